@@ -10,14 +10,18 @@ streaming batches through the public API would run them (extras.single_lane keep
 one-stream protocol of rounds 1-3).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--frames B] [--nms off|maxt|sad]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one process per GPU)
 
-Besides the headline value the line carries: the roofline of the detector (HIP events on the
-lane streams; algorithmic bytes = W*H + 8*K + 4 per frame), single-frame
-latencies, whole-batch parity (every frame of every input copy against the CPU checker, on
-every rank, all-reduced), and the CPU baseline (the AVX2 port of the reference path,
-oracle/fast_avx2.cpp, rank 0, N=1).  Each lane reads its own copy of the batch (different
-rolls of the S1 frames), so no two launches in flight share input bytes.
+A plain run does what the headline needs and no more: it builds the batch, settles the
+clocks, warms up, times the K steps, writes the last step's result with --dump-outputs, and
+prints the line (value, ms_per_step, the keypoints per step and the roofline of the timed
+region's own HIP-event span).  With --full the line also carries: the launches' own durations
+(a sampling region before the timed one), single-frame latencies, whole-batch parity (every
+frame of every input copy against the CPU checker, on every rank, all-reduced), the other NMS
+modes, the one-lane, 4K, RGB and shard legs, and the CPU baseline (the AVX2 port of the
+reference path, oracle/fast_avx2.cpp, rank 0, N=1).  Each lane reads its own copy of the batch
+(different rolls of the S1 frames), so no two launches in flight share input bytes.
 """
 import argparse
 import json
@@ -37,6 +41,7 @@ HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s mea
 # launches' own durations in a region of their own: a timestamped dispatch costs queue time)
 MIN_TIMED = 10
 NMS_NAMES = {"off": 0, "maxt": 1, "sad": 2}
+DUMP_MAX_BYTES = 48 << 20    # --dump-outputs: more points than this are sampled (seeded)
 
 
 def parse_args(argv=None):
@@ -58,6 +63,12 @@ def parse_args(argv=None):
     p.add_argument("--nms", choices=sorted(NMS_NAMES), default="maxt")
     p.add_argument("--cpu-seconds", type=float, default=10.0,
                    help="budget for the single-thread CPU baseline sample (0 = skip)")
+    p.add_argument("--full", action="store_true",
+                   help="besides the headline: the launch-duration sampling region, whole-batch "
+                        "parity, the extras legs and the CPU baseline (off: the timed steps alone)")
+    p.add_argument("--dump-outputs", metavar="DIR", default="",
+                   help="after the timed steps, write the last step's result (this rank's "
+                        "offsets and points) as DIR/<name>.npy")
     p.add_argument("--no-extras", action="store_true", help="skip the latency/leg extras")
     p.add_argument("--no-parity", action="store_true",
                    help="skip the whole-batch parity check of the headline (experiments only)")
@@ -79,7 +90,12 @@ def parse_args(argv=None):
                    help="an image (PNG/PGM, converted as image 0.24.6 to_luma8) for the "
                         "single-frame GPU and CPU legs, as the reference's bench takes "
                         "INPUT_FILE (benches/benchmark.rs:6-7); the batch stays synthetic")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if not args.full:
+        # a plain run: the timed steps alone
+        args.no_extras = args.no_parity = args.no_strong_leg = True
+        args.cpu_seconds = 0.0
+    return args
 
 
 # torch.distributed's reductions run on this device ("cpu" under gloo when ranks share a GPU)
@@ -641,8 +657,8 @@ def roofline_of(t, alg_bytes, in_bytes, traffic):
         from the same calls in a sampling region before the timed one (timed_steps).
     Percentiles only from >= MIN_TIMED samples (fewer: the mean alone)."""
     per_launch = t.span_ms / t.steps
-    launch = float(np.mean(t.det)) if len(t.det) else float("nan")
-    comp = float(np.mean(t.com)) if len(t.com) else float("nan")
+    launch = float(np.mean(t.det)) if len(t.det) else None
+    comp = float(np.mean(t.com)) if len(t.com) else None
     achieved = alg_bytes / (per_launch * 1e-3) / 1e9
     tbytes, tstamp = traffic
     enough = len(t.det) >= MIN_TIMED
@@ -653,14 +669,15 @@ def roofline_of(t, alg_bytes, in_bytes, traffic):
             "kernel": "fast_sweep_kernel", "kernel_ms_avg": round(per_launch, 4),
             "kernel_ms_basis": f"HIP-event span of {t.steps} launches on {t.lanes} lane stream(s) / launches",
             "lanes": t.lanes,
-            "launch_ms_avg": round(launch, 4),
+            "launch_ms_avg": round(launch, 4) if launch is not None else None,
             "launch_ms": percentiles(t.det) if enough else None,
-            "launches_in_flight_avg": round(launch / per_launch, 3) if per_launch > 0 else None,
+            "launches_in_flight_avg": round(launch / per_launch, 3)
+            if launch is not None and per_launch > 0 else None,
             "timed_launches": int(len(t.det)),
             "alg_bytes_per_launch": int(alg_bytes),
             "input_bytes_per_launch": int(in_bytes),
             "frac_input_bytes_only": round(in_bytes / (per_launch * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-            "compaction_kernel_ms_avg": round(comp, 4),
+            "compaction_kernel_ms_avg": round(comp, 4) if comp is not None else None,
             "compaction_kernel_ms": percentiles(t.com) if enough else None,
             "measured_achievable_peak": 6290.0}
 
@@ -767,6 +784,27 @@ def shard_leg(fast_hip, workloads, oracle, lanes, cfg, args, world, device, firs
     return t, e, par, kp, roof
 
 
+def dump_outputs(path, bufs, tm, count, world, rank):
+    """--dump-outputs: what the last timed step returned to its caller, i.e. the offsets and
+    points in the buffers of the lane that ran it, as float64 / float32 .npy files under
+    `path` (every rank its own shard, named *_rank<r> when there are several).  More points
+    than DUMP_MAX_BYTES holds are cut to a fixed, seeded sample of rows (in order); `meta`
+    = [lane, input copy, points in all, points written]."""
+    lane = tm.last
+    offs = bufs.offs[lane][: count + 1].cpu().numpy().astype(np.float64)
+    total = min(int(offs[-1]), bufs.out[lane].shape[0])
+    pts = bufs.out[lane][:total].cpu().numpy().astype(np.float32)
+    keep = DUMP_MAX_BYTES // (2 * 4)
+    if total > keep:
+        rows = np.sort(np.random.Generator(np.random.PCG64(0)).choice(total, keep, replace=False))
+        pts = pts[rows]
+    meta = np.array([lane, tm.lane_copy.get(lane, 0), total, len(pts)], dtype=np.float64)
+    os.makedirs(path, exist_ok=True)
+    tag = f"_rank{rank}" if world > 1 else ""
+    for name, a in (("offsets", offs), ("points", pts), ("meta", meta)):
+        np.save(os.path.join(path, f"{name}{tag}.npy"), a)
+
+
 def select_device(ranks_share_device, world, local):
     """(GPU index, process-group backend or None) of this rank: one process per GPU, rank
     with LOCAL_RANK r on cuda:r over the default backend ("nccl" = RCCL on ROCm); with
@@ -823,14 +861,22 @@ def main(argv=None):
     out, offs = bufs.out[0], bufs.offs[0]
 
     tm = timed_steps(fast_hip, lanes, bufs, copies, cfg, args.steps, args.warmup, world,
-                     settle=args.settle_seconds, inline=args.inline_timing)
+                     settle=args.settle_seconds, sample=args.full or args.inline_timing,
+                     inline=args.inline_timing)
     elapsed = reduce_max(tm.elapsed, world, device)
+    if args.dump_outputs:
+        # before anything below reuses the lanes' buffers
+        dump_outputs(args.dump_outputs, bufs, tm, count, world, rank)
 
     # ---- whole-batch parity against the CPU checker (outside the timed region), on every
     # rank for its own shard, all-reduced
     parity = {}
     if args.no_parity:
-        kp_step = float(np.mean([int(bufs.offs[i][count].item()) for i in tm.lane_copy]))
+        # the lanes' last results, weighted by the steps that read each one's copy (as the
+        # checker's totals are below; copies no lane read last are left out)
+        kp_copy = {c: int(bufs.offs[i][count].item()) for i, c in tm.lane_copy.items()}
+        kp_step = (sum(k * tm.copy_steps.get(c, 0) for c, k in kp_copy.items())
+                   / max(1, sum(tm.copy_steps.get(c, 0) for c in kp_copy)))
     else:
         parity, kp_step = batch_parity(oracle, copies, bufs, tm, args.threshold, args.count,
                                        nms, W, redo=redo_on_lane0(lanes, bufs, copies, cfg))
@@ -856,7 +902,8 @@ def main(argv=None):
     roofline = roofline_of(tm, alg_bytes, in_bytes, load_traffic(cfg_key, len(lanes)))
     roofline["launch_ms_source"] = ("the timed region's own dispatches, timestamped" if args.inline_timing
                                     else "the same calls in a sampling region before the timed one "
-                                         "(the timed region's dispatches are not timestamped)")
+                                         "(the timed region's dispatches are not timestamped)"
+                                    if args.full else None)
 
     extras = {}
     cpu = None
@@ -1003,7 +1050,7 @@ def main(argv=None):
         line = {
             "metric": METRIC, "value": round(value, 1), "unit": "Mpixels/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "settle_seconds": args.settle_seconds,
+            "settle_seconds": args.settle_seconds, "full": bool(args.full),
             "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
             "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "u8",
             "data": "synthetic S1 (committed 300x200 golden fixture tiled, rolled per frame; one distinct copy of the batch per lane)",

@@ -77,6 +77,51 @@ def test_roofline_from_timed_region():
     assert r4["launch_ms"] is None and r4["compaction_kernel_ms"] is None    # mean only
 
 
+def test_plain_run_is_the_timed_steps_alone():
+    """Without --full nothing but the headline runs: no parity, extras, strong leg or CPU
+    baseline, whatever else is given; --full keeps the defaults of each."""
+    plain = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2", "--cpu-seconds", "5"])
+    assert plain.steps == 7 and plain.warmup == 2 and not plain.full and not plain.dump_outputs
+    assert plain.no_extras and plain.no_parity and plain.no_strong_leg and plain.cpu_seconds == 0
+    full = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert full.full and full.dump_outputs == "d"
+    assert not (full.no_extras or full.no_parity or full.no_strong_leg) and full.cpu_seconds == 10.0
+    assert bench.parse_args(["--full", "--no-extras"]).no_extras
+    # a timed region without the sampling region: the span's figures, no launch durations
+    t = bench.Timed(0.0081, 8.0, [], [], 1, 20, 3)
+    r = bench.roofline_of(t, 2_000, 1_000, (None, None))
+    assert r["kernel_ms_avg"] == pytest.approx(0.4) and r["timed_launches"] == 0
+    assert r["launch_ms_avg"] is None and r["compaction_kernel_ms_avg"] is None
+    assert r["launches_in_flight_avg"] is None and r["launch_ms"] is None
+
+
+def test_dump_outputs_writes_the_last_steps_result(tmp_path, monkeypatch):
+    """--dump-outputs: the offsets and points of the lane that ran the last timed step, as
+    float .npy files; more points than the size cap become the same seeded sample each time."""
+    import numpy as np
+    import torch
+
+    class Bufs:
+        pass
+
+    b = Bufs()
+    pts = np.arange(40, dtype=np.int32).reshape(20, 2)
+    b.out = [torch.zeros((30, 2), dtype=torch.int32), torch.from_numpy(np.concatenate([pts, pts[:10]]))]
+    b.offs = [torch.zeros(4, dtype=torch.int64), torch.tensor([0, 5, 5, 20, 99], dtype=torch.int64)]
+    tm = bench.Timed(0.01, 1.0, [], [], 1, 5, 2, lane_copy={0: 0, 1: 3})
+    bench.dump_outputs(str(tmp_path / "a"), b, tm, 3, 1, 0)
+    offs, got, meta = (np.load(tmp_path / "a" / f"{n}.npy") for n in ("offsets", "points", "meta"))
+    assert offs.dtype == np.float64 and offs.tolist() == [0, 5, 5, 20]
+    assert got.dtype == np.float32 and np.array_equal(got, pts)
+    assert meta.tolist() == [1, 3, 20, 20]
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 8 * 8)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), b, tm, 3, 2, 1)
+    s1, s2 = (np.load(tmp_path / d / "points_rank1.npy") for d in ("b", "c"))
+    assert s1.shape == (8, 2) and np.array_equal(s1, s2)
+    assert np.all(np.diff(s1[:, 0]) > 0) and np.load(tmp_path / "b" / "meta_rank1.npy")[3] == 8
+
+
 def test_batch_parity_checks_every_frame():
     """bench.batch_parity on CPU tensors: each lane's last result equal to
     the checker on every frame passes; one moved point in any frame of any lane fails, and so

@@ -28,7 +28,8 @@ def test_torchrun_two_ranks_share_device():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--frames", "64", "--steps", "5",
-           "--warmup", "2", "--settle-seconds", "0", "--no-extras", "--ranks-share-device"]
+           "--warmup", "2", "--settle-seconds", "0", "--full", "--no-extras",
+           "--ranks-share-device"]
     env = dict(os.environ, OMP_NUM_THREADS="2")
     res = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     if res.returncode != 0:       # the ranks' own tracebacks, not torchrun's summary

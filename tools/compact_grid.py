@@ -23,7 +23,7 @@ for w, h, f, t, n, nms in GRID:
     with contextlib.redirect_stdout(buf):
         bench.main(["--width", w, "--height", h, "--frames", f, "--threshold", t, "--count", n,
                     "--nms", nms, "--steps", "10", "--warmup", "3", "--cpu-seconds", "0",
-                    "--no-extras"])
+                    "--full", "--no-extras"])
     d = json.loads(buf.getvalue().strip().splitlines()[-1])
     r = d["roofline"]
     print(f"{w}x{h} b{f} t{t} n{n} {nms}: sweep {r['kernel_ms_avg']} ms, compact "

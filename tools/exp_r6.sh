@@ -18,7 +18,7 @@ exp_c5ab() {
   for r in 1 2 3; do
     for lc in "1 1" "1 3" "3 1" "3 3"; do
       set -- $lc
-      timeout -k 10 150 python3 bench.py $C5 --lanes $1 --copies $2 --no-extras --no-parity \
+      timeout -k 10 150 python3 bench.py $C5 --lanes $1 --copies $2 --full --no-extras --no-parity \
           --cpu-seconds 0 --steps 30 --warmup 5 > $O/run.json 2> $O/run.err
       python3 -c "import json,sys; d=json.load(open('$O/run.json')); r=d['roofline']; print(json.dumps({'round': $r, 'lanes': $1, 'copies': $2, 'ms_per_step': d['ms_per_step'], 'kernel_ms_avg': r['kernel_ms_avg'], 'launch_ms_avg': r['launch_ms_avg']}))" >> $O/ab.jsonl
     done
@@ -61,7 +61,7 @@ exp_timing_ab() {
   for r in 1 2 3; do
     for mode in separate inline; do
       extra=""; [ $mode = inline ] && extra="--inline-timing"
-      timeout -k 10 200 python3 bench.py --no-extras --no-parity --cpu-seconds 0 $extra > $O/run.json 2> $O/run.err
+      timeout -k 10 200 python3 bench.py --full --no-extras --no-parity --cpu-seconds 0 $extra > $O/run.json 2> $O/run.err
       python3 -c "import json; d=json.load(open('$O/run.json')); r=d['roofline']; print(json.dumps({'round': $r, 'mode': '$mode', 'value': d['value'], 'ms_per_step': d['ms_per_step'], 'kernel_ms_avg': r['kernel_ms_avg'], 'launch_ms_avg': r['launch_ms_avg']}))" >> $O/ab.jsonl
     done
   done

@@ -6,6 +6,7 @@
 #   testslib|LIB|EXPR                  the same on another build of the library (FDF_LIB_PATH)
 #   smoke                              __graft_entry__.smoke()
 #   bench|NAME|ARGS                    python bench.py ARGS            -> NAME.json
+#                                      (--full among ARGS: parity, extras legs, CPU baseline)
 #   ab|NAME|ROUNDS|VARIANTS|ARGS|LIBS  interleaved A/B of library builds (LIBS comma-separated,
 #                                      tools/ablate.py variants)       -> NAME.txt
 #   ablate|NAME|ARGS                   tools/ablate.py ARGS on the debug build -> NAME.json
