@@ -40,7 +40,8 @@ EXPORTED_SYMBOLS = (
     "fdf_detect_batch_multi", "fdf_fetch_last_multi", "fdf_ctx_workspace_bytes",
     "fdf_detect_device_rgb", "fdf_circle", "fdf_calculate_offsets", "fdf_score_rings",
     "fdf_score_rings_device", "fdf_ctx_set_band_rows", "fdf_ctx_set_upload_chunks",
-    "fdf_ctx_recoveries", "fdf_ctx_test_skew_tickets",
+    "fdf_ctx_recoveries", "fdf_ctx_test_skew_tickets", "fdf_select_scratch_bytes",
+    "fdf_select_device", "fdf_select_points",
 )
 
 
@@ -179,6 +180,14 @@ def load():
                                            ctypes.POINTER(sz)]
     lib.fdf_fetch_last_multi.restype = ctypes.c_int
     lib.fdf_fetch_last_multi.argtypes = [vp, u32, vp, sz, ctypes.POINTER(sz)]
+    lib.fdf_select_scratch_bytes.restype = ctypes.c_int
+    lib.fdf_select_scratch_bytes.argtypes = [u32, u32, u32, u32, u32, u64, ctypes.POINTER(u64)]
+    lib.fdf_select_device.restype = ctypes.c_int
+    lib.fdf_select_device.argtypes = [vp, u32, u32, u32, vp, vp, u64, vp, u32, u32, u32, vp, vp,
+                                      u64, vp, vp, vp, u64, vp]
+    lib.fdf_select_points.restype = ctypes.c_int
+    lib.fdf_select_points.argtypes = [vp, vp, vp, vp, u32, sz, u32, u32, u32, u32, u32, vp, vp,
+                                      sz, vp, ctypes.POINTER(sz)]
     del u8p
     _lib = lib
     return lib

@@ -1443,6 +1443,191 @@ int fdf_score_points(fdf_ctx* ctx, const uint8_t* data, uint32_t width, uint32_t
     return e == hipSuccess ? FDF_OK : FDF_ERR_DEVICE;
 }
 
+// ---- best-K selection per grid cell (fdf_select.hip) -------------------------------------
+namespace {
+
+// Scratch of one fdf_select_device call, every part 256-byte aligned: the per-frame kept
+// totals (zeroed on the stream before the kernels), the kept count and the index range of
+// every (frame, cell row), and `cap` keep flags for a caller that passes no d_keep.
+struct SelectLayout {
+    uint32_t cw = 0, ch = 0, cells_x = 0, rows = 0;
+    uint64_t frame_tot = 0, row_cnt = 0, row_range = 0, keep = 0, total = 0;
+};
+
+inline uint64_t align256(uint64_t v) { return (v + 255u) & ~255ull; }
+
+// FDF_OK with *empty set for shapes with no keypoints; the shape's error otherwise.
+int select_layout(uint32_t n_frames, uint32_t width, uint32_t height, uint32_t cell_w,
+                  uint32_t cell_h, uint64_t cap, SelectLayout* L, int* empty) {
+    int rc = check_shape(width, height, empty);
+    if (rc) return rc;
+    if (n_frames > 65535u || (uint64_t)width * height > 0xffffffffull) return FDF_ERR_ARG;
+    if (n_frames == 0) *empty = 1;
+    if (*empty) return FDF_OK;
+    L->cw = cell_w == 0 || cell_w > width ? width : cell_w;
+    L->ch = cell_h == 0 || cell_h > height ? height : cell_h;
+    L->cells_x = (width + L->cw - 1) / L->cw;
+    L->rows = (height + L->ch - 1) / L->ch;
+    if (L->rows > fdfk::kSelMaxRows) return FDF_ERR_ARG;
+    const uint64_t nrows = (uint64_t)n_frames * L->rows;
+    L->frame_tot = 0;
+    L->row_cnt = align256(sizeof(uint64_t) * n_frames);
+    L->row_range = L->row_cnt + align256(sizeof(uint32_t) * nrows);
+    L->keep = L->row_range + align256(2 * sizeof(uint64_t) * nrows);
+    if (cap > ~0ull - L->keep - 256u) return FDF_ERR_ARG;
+    L->total = L->keep + align256(cap);
+    return FDF_OK;
+}
+
+}  // namespace
+
+int fdf_select_scratch_bytes(uint32_t n_frames, uint32_t width, uint32_t height,
+                             uint32_t cell_w, uint32_t cell_h, uint64_t cap, uint64_t* bytes) {
+    if (!bytes) return FDF_ERR_ARG;
+    SelectLayout L;
+    int empty = 0;
+    const int rc = select_layout(n_frames, width, height, cell_w, cell_h, cap, &L, &empty);
+    if (rc) return rc;
+    *bytes = empty ? 0 : L.total;
+    return FDF_OK;
+}
+
+int fdf_select_device(fdf_ctx* ctx, uint32_t n_frames, uint32_t width, uint32_t height,
+                      const fdf_point* d_points, const uint16_t* d_scores, uint64_t cap,
+                      const uint64_t* d_frame_offsets, uint32_t cell_w, uint32_t cell_h,
+                      uint32_t k, fdf_point* d_sel, uint16_t* d_sel_scores, uint64_t sel_cap,
+                      uint64_t* d_sel_offsets, uint8_t* d_keep, void* d_scratch,
+                      uint64_t scratch_bytes, void* stream) {
+    if (!ctx || !d_sel_offsets || k == 0) return FDF_ERR_ARG;
+    SelectLayout L;
+    int empty = 0;
+    const int rc = select_layout(n_frames, width, height, cell_w, cell_h, cap, &L, &empty);
+    if (rc) return rc;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);   // NULL = the HIP null stream
+    if (!empty) {
+        if (!d_frame_offsets || !d_scratch || scratch_bytes < L.total ||
+            ((uintptr_t)d_scratch & 255u) != 0)
+            return FDF_ERR_ARG;
+        if (cap && (!d_points || !d_scores)) return FDF_ERR_ARG;
+        if (sel_cap && (!d_sel || !d_sel_scores)) return FDF_ERR_ARG;
+    }
+    DeviceGuard guard(ctx->device);
+    if (empty || cap == 0) {
+        return hipMemsetAsync(d_sel_offsets, 0, sizeof(uint64_t) * (n_frames + 1ull), s) ==
+                       hipSuccess
+                   ? FDF_OK
+                   : FDF_ERR_DEVICE;
+    }
+    uint8_t* base = static_cast<uint8_t*>(d_scratch);
+    fdfk::SelectParams p{};
+    p.pts = reinterpret_cast<const uint2*>(d_points);
+    p.scores = d_scores;
+    p.offs = d_frame_offsets;
+    p.cap = cap;
+    p.n_frames = n_frames;
+    p.cw = L.cw;
+    p.ch = L.ch;
+    p.cells_x = L.cells_x;
+    p.rows = L.rows;
+    p.k = k;
+    p.keep = d_keep ? d_keep : base + L.keep;
+    p.frame_tot = reinterpret_cast<uint64_t*>(base + L.frame_tot);
+    p.row_cnt = reinterpret_cast<uint32_t*>(base + L.row_cnt);
+    p.row_range = reinterpret_cast<uint64_t*>(base + L.row_range);
+    p.sel = reinterpret_cast<uint2*>(d_sel);
+    p.sel_scores = d_sel_scores;
+    p.sel_cap = sel_cap;
+    p.sel_offs = d_sel_offsets;
+    // the frame totals are summed into; the keep flags of indices no frame owns stay 0
+    hipError_t e = hipMemsetAsync(p.frame_tot, 0, sizeof(uint64_t) * n_frames, s);
+    if (e == hipSuccess) e = hipMemsetAsync(p.keep, 0, cap, s);
+    if (e == hipSuccess) e = fdfk::launch_select(p, s);
+    return e == hipSuccess ? FDF_OK : FDF_ERR_DEVICE;
+}
+
+int fdf_select_points(fdf_ctx* ctx, const fdf_point* points, const uint16_t* scores,
+                      const uint64_t* frame_offsets, uint32_t n_frames, size_t n_points,
+                      uint32_t width, uint32_t height, uint32_t cell_w, uint32_t cell_h,
+                      uint32_t k, fdf_point* out, uint16_t* out_scores, size_t cap,
+                      uint64_t* out_offsets, size_t* n_out) {
+    if (!ctx || !n_out || k == 0) return FDF_ERR_ARG;
+    if (n_points && (!points || !scores)) return FDF_ERR_ARG;
+    if (cap && (!out || !out_scores)) return FDF_ERR_ARG;
+    if (!frame_offsets && n_frames != 1) return FDF_ERR_ARG;
+    SelectLayout L;
+    int empty = 0;
+    const int rc = select_layout(n_frames, width, height, cell_w, cell_h, n_points, &L, &empty);
+    if (rc) return rc;
+    *n_out = 0;
+    if (empty || n_points == 0) {
+        if (out_offsets) std::memset(out_offsets, 0, sizeof(uint64_t) * (n_frames + 1ull));
+        return FDF_OK;
+    }
+    // one allocation for the call, cut into 256-byte aligned parts; the context's workspace
+    // and retained result (fdf_fetch_last) are not touched
+    const uint64_t noffs = n_frames + 1ull;
+    const uint64_t o_pts = 0;
+    const uint64_t o_scores = o_pts + align256(n_points * sizeof(fdf_point));
+    const uint64_t o_offs = o_scores + align256(n_points * sizeof(uint16_t));
+    const uint64_t o_sel = o_offs + align256(noffs * sizeof(uint64_t));
+    const uint64_t o_sel_scores = o_sel + align256((uint64_t)cap * sizeof(fdf_point));
+    const uint64_t o_sel_offs = o_sel_scores + align256((uint64_t)cap * sizeof(uint16_t));
+    const uint64_t o_scratch = o_sel_offs + align256(noffs * sizeof(uint64_t));
+    const uint64_t bytes = o_scratch + L.total;
+    std::lock_guard<std::mutex> lock(ctx->mu);    // the context's stream carries the call
+    DeviceGuard guard(ctx->device);
+    uint8_t* d = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&d), bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return FDF_ERR_ALLOC;
+    }
+    const uint64_t one_frame[2] = {0, n_points};
+    std::vector<uint64_t> offs(noffs);
+    hipStream_t s = ctx->stream;
+    hipError_t e = hipMemcpyAsync(d + o_pts, points, n_points * sizeof(fdf_point),
+                                  hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(d + o_scores, scores, n_points * sizeof(uint16_t),
+                           hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(d + o_offs, frame_offsets ? frame_offsets : one_frame,
+                           noffs * sizeof(uint64_t), hipMemcpyHostToDevice, s);
+    int status = FDF_OK;
+    if (e == hipSuccess)
+        status = fdf_select_device(ctx, n_frames, width, height,
+                                   reinterpret_cast<const fdf_point*>(d + o_pts),
+                                   reinterpret_cast<const uint16_t*>(d + o_scores), n_points,
+                                   reinterpret_cast<const uint64_t*>(d + o_offs), cell_w, cell_h,
+                                   k, reinterpret_cast<fdf_point*>(d + o_sel),
+                                   reinterpret_cast<uint16_t*>(d + o_sel_scores), cap,
+                                   reinterpret_cast<uint64_t*>(d + o_sel_offs), nullptr,
+                                   d + o_scratch, L.total, s);
+    if (e == hipSuccess && status == FDF_OK)
+        e = hipMemcpyAsync(offs.data(), d + o_sel_offs, noffs * sizeof(uint64_t),
+                           hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && status == FDF_OK) e = hipStreamSynchronize(s);
+    if (e == hipSuccess && status == FDF_OK) {
+        const uint64_t total = offs[n_frames];
+        const uint64_t ncopy = std::min<uint64_t>(total, cap);
+        if (ncopy) {
+            e = hipMemcpyAsync(out, d + o_sel, ncopy * sizeof(fdf_point), hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(out_scores, d + o_sel_scores, ncopy * sizeof(uint16_t),
+                                   hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
+        }
+        if (e == hipSuccess) {
+            *n_out = (size_t)total;
+            if (out_offsets) std::memcpy(out_offsets, offs.data(), noffs * sizeof(uint64_t));
+            if (total > cap) status = FDF_ERR_CAPACITY;
+        }
+    }
+    if (e != hipSuccess) (void)hipStreamSynchronize(s);    // nothing may still use `d`
+    (void)hipFree(d);
+    if (e != hipSuccess) return FDF_ERR_DEVICE;
+    return status;
+}
+
 // ---- ring-level helpers (src/fast_simd.rs:69-110, :623, :722) ---------------------------
 
 static constexpr int32_t kCircleDx[16] = {0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1};

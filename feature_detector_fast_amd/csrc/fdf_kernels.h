@@ -1,5 +1,6 @@
-// fdf_kernels.h -- shared between the HIP kernels (fdf_sweep.hip, fdf_kernels.hip) and the
-// C-ABI host layer (fdf_api.cpp): geometry constants, LDS layout and launch parameters.
+// fdf_kernels.h -- shared between the HIP kernels (fdf_sweep.hip, fdf_kernels.hip,
+// fdf_select.hip) and the C-ABI host layer (fdf_api.cpp): geometry constants, LDS layout and
+// launch parameters.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -254,5 +255,31 @@ hipError_t launch_score_frames(const uint8_t* frames, uint32_t width, uint64_t f
                                uint32_t n_frames, const uint2* pts, const uint64_t* offsets,
                                uint64_t cap, uint32_t blocks_per_frame, uint32_t nms,
                                uint32_t t, uint32_t n, uint16_t* out, hipStream_t stream);
+
+// Best-K selection per grid cell (fdf_select.hip; fdf_select_device).
+constexpr int kSelThreads = 256;
+constexpr int kSelWaves = kSelThreads / 64;
+constexpr int kSelCells = 16;                 // cells of a row handled at once (16 KB of LDS)
+constexpr uint32_t kSelMaxRows = 1u << 23;    // cell rows (grid.x): rows * 256 threads < 2^32
+struct SelectParams {
+    const uint2* pts;            // `cap` points, frames concatenated, each in raster order
+    const uint16_t* scores;      // `cap` scores
+    const uint64_t* offs;        // n_frames + 1 entries
+    uint64_t cap;
+    uint32_t n_frames;
+    uint32_t cw, ch;             // cell size in pixels (>= 1)
+    uint32_t cells_x, rows;      // cells per cell row, cell rows per frame
+    uint32_t k;
+    uint8_t* keep;               // `cap` flags (the caller's, or in the scratch)
+    uint64_t* frame_tot;         // scratch: n_frames kept totals, zero before the launch
+    uint32_t* row_cnt;           // scratch: kept points per (frame, cell row)
+    uint64_t* row_range;         // scratch: [lo, hi) index range per (frame, cell row)
+    uint2* sel;
+    uint16_t* sel_scores;
+    uint64_t sel_cap;
+    uint64_t* sel_offs;          // n_frames + 1 entries
+};
+// select, scan and scatter kernels on `stream` (frame_tot already zeroed there)
+hipError_t launch_select(const SelectParams& p, hipStream_t stream);
 
 }  // namespace fdfk

@@ -549,11 +549,150 @@ def score_device(frames, config, points, offsets, scores, stream=None, device=No
         ctypes.c_void_p(stream.cuda_stream))
     check(rc, "fdf_score_device")
 
+def _cell_k(cell, k):
+    """(cell_w, cell_h, k) of a selection: ``cell`` is (cell_w, cell_h), 0 meaning the whole
+    image dimension; k >= 1."""
+    cw, ch = (int(v) for v in cell)
+    k = int(k)
+    if cw < 0 or ch < 0 or cw > 0xffffffff or ch > 0xffffffff:
+        raise ValueError("cell sizes must fit in u32")
+    if not 1 <= k <= 0xffffffff:
+        raise ValueError("k must be at least 1")
+    return cw, ch, k
+
+
+def select_scratch_bytes(n_frames, shape, cell, cap):
+    """Scratch bytes select_device needs (fdf_select_scratch_bytes; host only, no device):
+    ``shape`` is (height, width), ``cell`` (cell_w, cell_h), ``cap`` the points' capacity."""
+    h, w = (int(v) for v in shape)
+    cw, ch = (int(v) for v in cell)
+    v = ctypes.c_uint64()
+    check(_native.load().fdf_select_scratch_bytes(int(n_frames), w, h, cw, ch, int(cap),
+                                                  ctypes.byref(v)), "fdf_select_scratch_bytes")
+    return v.value
+
+
+def select_device(points, scores, offsets, shape, cell, k, sel, sel_scores, sel_offsets,
+                  keep=None, scratch=None, stream=None):
+    """Best ``k`` points per ``cell`` = (cell_w, cell_h) grid cell of every frame, on the
+    device (fdf_select_device): ``points`` (cap, 2), ``scores`` (cap,) 16-bit and ``offsets``
+    (F+1,) int64 (exactly F+1 entries: F is taken from it) as detect_device and score_device
+    filled them, ``shape`` = (height, width).
+    The kept points go to ``sel`` (sel_cap, 2) and ``sel_scores`` (sel_cap,) in input order,
+    ``sel_offsets`` (F+1,) int64 gets the per-frame prefix and the full total; ``keep``
+    (optional, (cap,) uint8) gets a 1 / 0 flag per input point.  Ties at the cut go to the
+    earlier point.  ``scratch``: a uint8 CUDA tensor of at least select_scratch_bytes(...)
+    bytes (None: allocated through torch).  Asynchronous on ``stream`` (default: torch's
+    current stream)."""
+    import torch
+
+    cw, ch, k = _cell_k(cell, k)
+    h, w = (int(v) for v in shape)
+    for name, t in (("points", points), ("sel", sel)):
+        if t.dim() != 2 or t.shape[1] != 2 or t.element_size() != 4 or not t.is_contiguous() \
+                or t.is_floating_point():
+            raise ValueError(f"{name} must be a contiguous (n, 2) 32-bit integer tensor")
+    for name, t, n in (("scores", scores, points.shape[0]), ("sel_scores", sel_scores, sel.shape[0])):
+        if t.dim() != 1 or t.element_size() != 2 or not t.is_contiguous() or \
+                t.is_floating_point() or t.numel() < n:
+            raise ValueError(f"{name} must be a contiguous 16-bit integer tensor, one entry per point")
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 2 or \
+            not offsets.is_contiguous():
+        raise ValueError("offsets must be a contiguous int64 tensor with F+1 entries")
+    f = offsets.numel() - 1
+    if sel_offsets.dtype != torch.int64 or sel_offsets.numel() < f + 1 or \
+            not sel_offsets.is_contiguous():
+        raise ValueError("sel_offsets must be a contiguous int64 tensor with F+1 entries")
+    cap = points.shape[0]
+    if keep is not None and (keep.dtype != torch.uint8 or keep.numel() < cap or
+                             not keep.is_contiguous()):
+        raise ValueError("keep must be a contiguous uint8 tensor with cap entries")
+    tensors = [points, scores, offsets, sel, sel_scores, sel_offsets]
+    if keep is not None:
+        tensors.append(keep)
+    if scratch is not None:
+        tensors.append(scratch)
+    if not all(t.is_cuda for t in tensors) or len({t.device for t in tensors}) != 1:
+        raise ValueError("select_device needs CUDA (HIP) tensors on one device")
+    need = select_scratch_bytes(f, (h, w), (cw, ch), cap)
+    if scratch is not None and (scratch.dtype != torch.uint8 or not scratch.is_contiguous()):
+        raise ValueError("scratch must be a contiguous uint8 tensor")
+    current = torch.cuda.current_stream(points.device)
+    if stream is None:
+        stream = current
+    if scratch is None:
+        scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=points.device)
+        if stream != current:
+            # the caching allocator hands a freed block to the next request of the current
+            # stream; this one is in use on `stream` until the call's kernels are done
+            scratch.record_stream(stream)
+    rc = _native.load().fdf_select_device(
+        context(points.device.index).handle, f, w, h, points.data_ptr(), scores.data_ptr(), cap,
+        offsets.data_ptr(), cw, ch, k, sel.data_ptr(), sel_scores.data_ptr(), sel.shape[0],
+        sel_offsets.data_ptr(), keep.data_ptr() if keep is not None else None,
+        scratch.data_ptr(), scratch.numel(), ctypes.c_void_p(stream.cuda_stream))
+    check(rc, "fdf_select_device")
+
+
+def select_best(points, scores, shape, cell, k, offsets=None, device=0):
+    """Best ``k`` points per ``cell`` = (cell_w, cell_h) grid cell (0 = the whole image
+    dimension) of raster-ordered ``points`` (K, 2) uint32 with ``scores`` (K,) uint16, for an
+    image of ``shape`` = (height, width), over fdf_select_points.  Returns (points, scores)
+    of the kept points in input order; with ``offsets`` ((F+1,) uint64, frames concatenated)
+    also the kept points' offsets."""
+    cw, ch, k = _cell_k(cell, k)
+    h, w = (int(v) for v in shape)
+    pts = np.asarray(points)
+    sc = np.asarray(scores)
+    if pts.dtype != np.uint32 or pts.ndim != 2 or pts.shape[1] != 2:
+        raise TypeError("points must be a (K, 2) uint32 array")
+    if sc.dtype != np.uint16 or sc.ndim != 1 or sc.shape[0] != pts.shape[0]:
+        raise TypeError("scores must be a (K,) uint16 array, one per point")
+    pts = np.ascontiguousarray(pts)
+    sc = np.ascontiguousarray(sc)
+    n = pts.shape[0]
+    if offsets is not None:
+        offs = np.asarray(offsets)
+        if offs.dtype != np.uint64 or offs.ndim != 1 or offs.shape[0] < 2:
+            raise TypeError("offsets must be a (F+1,) uint64 array")
+        offs = np.ascontiguousarray(offs)
+        f = offs.shape[0] - 1
+    else:
+        offs, f = None, 1
+    ctx = context(device)
+    lib = _native.load()
+    out_offs = np.zeros(f + 1, dtype=np.uint64)
+    cap = n                                   # a selection never exceeds its input
+    out = np.empty((cap, 2), dtype=np.uint32)
+    out_scores = np.empty(cap, dtype=np.uint16)
+    got = ctypes.c_size_t(0)
+    rc = lib.fdf_select_points(ctx.handle, pts.ctypes.data if n else None,
+                               sc.ctypes.data if n else None,
+                               offs.ctypes.data if offs is not None else None, f, n, w, h, cw, ch,
+                               k, out.ctypes.data if cap else None,
+                               out_scores.ctypes.data if cap else None, cap,
+                               out_offs.ctypes.data, ctypes.byref(got))
+    check(rc, "fdf_select_points")
+    m = got.value
+    if offsets is not None:
+        return out[:m], out_scores[:m], out_offs
+    return out[:m], out_scores[:m]
+
+
+def detect_best_array(img, config, cell, k, device=0):
+    """detect_scored_array followed by select_best: the ``k`` strongest keypoints of every
+    ``cell`` = (cell_w, cell_h) grid cell, as ((K, 2) uint32 in raster order, (K,) uint16)."""
+    cw, ch, k = _cell_k(cell, k)
+    arr = _as_pixels(img)
+    pts, scores = detect_scored_array(arr, config, device=device)
+    return select_best(pts, scores, arr.shape, (cw, ch), k, device=device)
+
 
 __all__ = ["NORTH", "EAST", "SOUTH", "WEST", "circle", "calculate_offsets", "context",
            "shard_contexts", "capacity_guess", "Lanes",
            "detect_array", "detector", "detector_batch", "detect_device", "keypoint_scores",
            "detect_scored_array", "detector_scored", "detector_batch_scored", "score_device",
+           "select_scratch_bytes", "select_device", "select_best", "detect_best_array",
            "detect_rgb_array", "detector_rgb", "rgb_to_luma", "detect_device_rgb",
            "score_rings", "score_rings_device", "keypoint_score_max_threshold",
            "keypoint_score_sum_abs_difference", "NonMaximalSuppression"]

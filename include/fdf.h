@@ -31,6 +31,8 @@
 extern "C" {
 #endif
 
+/* 6 still: fdf_select_scratch_bytes, fdf_select_device and fdf_select_points were added
+ * without changing any existing function, which is backward compatible. */
 #define FDF_ABI_VERSION 6
 
 /* Status codes.  Shapes the reference maps to an empty Vec return FDF_OK with 0 points. */
@@ -330,6 +332,60 @@ int fdf_score_device(fdf_ctx* ctx, const uint8_t* d_frames, uint32_t n_frames,
                      uint32_t width, uint32_t height, uint64_t frame_stride_bytes,
                      const fdf_config* cfg, const fdf_point* d_points, uint64_t cap,
                      const uint64_t* d_frame_offsets, uint16_t* d_scores, void* stream);
+
+/*
+ * Grid-bucketed best-K keypoint selection (extension: the reference returns every keypoint;
+ * its callers keep "the strongest K" or "the strongest K per grid cell").
+ *
+ * Input is what fdf_detect_device followed by fdf_score_device leave on the device: frame f
+ * owns the indices [offs[f], min(offs[f+1], cap)), in raster order, with x < width and
+ * y < height, and one u16 score per point (any u16 value).  Cells are cell_w x cell_h pixels
+ * (0 = the whole image dimension; cell_w = cell_h = 0 is "best K of the frame"):
+ * cells_x = ceil(width / cell_w), the cell of (x, y) is (y / cell_h) * cells_x + x / cell_w,
+ * and cells never span frames.  The rank of point i is the number of points j of its frame
+ * and cell with score[j] > score[i], or score[j] == score[i] and j < i; a point is kept iff
+ * its rank is below k (a stable sort by descending score; ties at the cut go to the earlier
+ * point).  The kept points of each frame are written in input order with their scores;
+ * d_sel_offsets[0..n_frames] is the exclusive prefix of the per-frame kept counts and
+ * d_sel_offsets[n_frames] the full total even when it exceeds sel_cap (entries at index
+ * >= sel_cap are not written), as fdf_detect_device does.  d_keep (optional, `cap` bytes)
+ * gets 1 for a kept point and 0 otherwise.  The result is a pure function of the inputs.
+ * Input that is not in raster order or lies outside the image gives an unspecified selection
+ * for its frame; no access leaves the caller's buffers.
+ *
+ * fdf_select_scratch_bytes: host only, no context or device needed; the scratch size
+ * fdf_select_device needs for these arguments (0 for the shapes the reference answers with an
+ * empty list and for n_frames == 0).  width * height < 2^32.
+ *
+ * fdf_select_device: asynchronous on `stream` (NULL = the HIP null stream, as for
+ * fdf_score_device); like that function it takes no context lock and uses no context
+ * workspace, it only binds the context's device.  Nothing is allocated and nothing returns
+ * to the host.  d_scratch (256-byte aligned, at least the queried size) needs no
+ * initialisation and may be reused by the next call in stream order.  FDF_ERR_ARG,
+ * synchronously and with nothing launched: k == 0, a NULL required pointer, a scratch that is
+ * too small or misaligned, n_frames > 65535.  Empty shapes and n_frames == 0 zero
+ * d_sel_offsets and return FDF_OK.
+ *
+ * fdf_select_points: host arrays in and out, synchronous.  frame_offsets (n_frames + 1
+ * entries) may be NULL for one frame of n_points points.  Two-call pattern as fdf_detect:
+ * FDF_ERR_CAPACITY with *n_out = the required count (the first `cap` are written).  Copies
+ * through device buffers allocated and freed by the call and runs the same kernels; the
+ * context's workspace and retained result are untouched, so fdf_fetch_last stays valid.
+ * out_offsets (n_frames + 1 entries) may be NULL.
+ */
+int fdf_select_scratch_bytes(uint32_t n_frames, uint32_t width, uint32_t height,
+                             uint32_t cell_w, uint32_t cell_h, uint64_t cap, uint64_t* bytes);
+int fdf_select_device(fdf_ctx* ctx, uint32_t n_frames, uint32_t width, uint32_t height,
+                      const fdf_point* d_points, const uint16_t* d_scores, uint64_t cap,
+                      const uint64_t* d_frame_offsets, uint32_t cell_w, uint32_t cell_h,
+                      uint32_t k, fdf_point* d_sel, uint16_t* d_sel_scores, uint64_t sel_cap,
+                      uint64_t* d_sel_offsets, uint8_t* d_keep, void* d_scratch,
+                      uint64_t scratch_bytes, void* stream);
+int fdf_select_points(fdf_ctx* ctx, const fdf_point* points, const uint16_t* scores,
+                      const uint64_t* frame_offsets, uint32_t n_frames, size_t n_points,
+                      uint32_t width, uint32_t height, uint32_t cell_w, uint32_t cell_h,
+                      uint32_t k, fdf_point* out, uint16_t* out_scores, size_t cap,
+                      uint64_t* out_offsets, size_t* n_out);
 
 /*
  * Streaming host pipeline (extension; the reference's callers detect on one

@@ -14,6 +14,7 @@
 //   keypoint_score_max_threshold    src/fast_simd.rs:623 fdf::fast_hip::keypoint_score_max_threshold
 //   keypoint_score_sum_abs_difference :722               fdf::fast_hip::keypoint_score_sum_abs_difference
 //   image::GrayImage                (image 0.24.6)       fdf::GrayView (borrowed row-major u8)
+//   (none: callers keep the best K)  --                   fdf::select_best(points, scores, ...)
 //
 // Where the reference panics (n < 9, n > 16, degenerate sizes) these throw fdf::Error.
 // Each thread lazily owns one device context per HIP device (device 0 unless
@@ -189,6 +190,32 @@ inline std::vector<Point> detector(const GrayView& img, const Config& config) {
     return detector(img, config, thread_context());
 }
 }  // namespace fast_hip
+
+// Best-K selection per grid cell (extension, fdf_select_points): of every cell_w x cell_h
+// cell (0 = the whole image dimension) of one frame's raster-ordered points, the k of highest
+// score, ties to the earlier point; the kept points in input order with their scores.
+inline std::pair<std::vector<Point>, std::vector<uint16_t>> select_best(
+    const std::vector<Point>& points, const std::vector<uint16_t>& scores, uint32_t width,
+    uint32_t height, uint32_t cell_w, uint32_t cell_h, uint32_t k, Context& ctx) {
+    if (points.size() != scores.size())
+        throw Error(FDF_ERR_ARG, "select_best: points and scores differ in length");
+    std::vector<Point> out(points.size());
+    std::vector<uint16_t> out_scores(points.size());
+    size_t n = 0;
+    check(fdf_select_points(ctx.get(), reinterpret_cast<const fdf_point*>(points.data()),
+                            scores.data(), nullptr, 1, points.size(), width, height, cell_w,
+                            cell_h, k, reinterpret_cast<fdf_point*>(out.data()),
+                            out_scores.data(), out.size(), nullptr, &n),
+          "fdf_select_points");
+    out.resize(n);
+    out_scores.resize(n);
+    return {std::move(out), std::move(out_scores)};
+}
+inline std::pair<std::vector<Point>, std::vector<uint16_t>> select_best(
+    const std::vector<Point>& points, const std::vector<uint16_t>& scores, uint32_t width,
+    uint32_t height, uint32_t cell_w, uint32_t cell_h, uint32_t k) {
+    return select_best(points, scores, width, height, cell_w, cell_h, k, thread_context());
+}
 
 inline std::vector<Point> detect(const GrayView& img, const Config& config) {
     return fast_hip::detector(img, config);
