@@ -41,7 +41,8 @@ EXPORTED_SYMBOLS = (
     "fdf_detect_device_rgb", "fdf_circle", "fdf_calculate_offsets", "fdf_score_rings",
     "fdf_score_rings_device", "fdf_ctx_set_band_rows", "fdf_ctx_set_upload_chunks",
     "fdf_ctx_recoveries", "fdf_ctx_test_skew_tickets", "fdf_select_scratch_bytes",
-    "fdf_select_device", "fdf_select_points",
+    "fdf_select_device", "fdf_select_points", "fdf_orient_disc", "fdf_orient_device",
+    "fdf_orient_points",
 )
 
 
@@ -188,6 +189,12 @@ def load():
     lib.fdf_select_points.restype = ctypes.c_int
     lib.fdf_select_points.argtypes = [vp, vp, vp, vp, u32, sz, u32, u32, u32, u32, u32, vp, vp,
                                       sz, vp, ctypes.POINTER(sz)]
+    lib.fdf_orient_disc.restype = ctypes.c_int
+    lib.fdf_orient_disc.argtypes = [u32, vp]
+    lib.fdf_orient_device.restype = ctypes.c_int
+    lib.fdf_orient_device.argtypes = [vp, vp, u32, u32, u32, u64, vp, u64, vp, u32, vp, vp, vp]
+    lib.fdf_orient_points.restype = ctypes.c_int
+    lib.fdf_orient_points.argtypes = [vp, vp, u32, u32, sz, vp, sz, u32, vp, vp]
     del u8p
     _lib = lib
     return lib

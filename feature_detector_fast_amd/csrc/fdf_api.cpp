@@ -8,6 +8,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <cstdint>
 #include <cstdlib>
 #include <cstdio>
@@ -1626,6 +1627,130 @@ int fdf_select_points(fdf_ctx* ctx, const fdf_point* points, const uint16_t* sco
     (void)hipFree(d);
     if (e != hipSuccess) return FDF_ERR_DEVICE;
     return status;
+}
+
+// ---- orientation by intensity centroid (fdf_orient.hip) ---------------------------------
+
+int fdf_orient_disc(uint32_t radius, uint8_t* half_widths) {
+    if (radius == 0 || radius > fdfk::kOrientMaxRadius || !half_widths) return FDF_ERR_ARG;
+    // OpenCV's umax: the rounded circle for the rows up to r / sqrt(2), mirrored for the rest
+    // so that the disc is symmetric about its diagonal
+    const int r = (int)radius;
+    const int vmax = (int)std::floor(r * std::sqrt(2.0) / 2 + 1);
+    const int vmin = (int)std::ceil(r * std::sqrt(2.0) / 2);
+    int u[fdfk::kOrientMaxRadius + 2] = {0};
+    for (int v = 0; v <= vmax; ++v)
+        u[v] = (int)std::floor(std::sqrt((double)r * r - (double)v * v) + 0.5);
+    for (int v = r, v0 = 0; v >= vmin; --v) {
+        while (u[v0] == u[v0 + 1]) ++v0;
+        u[v] = v0;
+        ++v0;
+    }
+    for (int v = 0; v <= r; ++v) half_widths[v] = (uint8_t)u[v];
+    return FDF_OK;
+}
+
+namespace {
+
+// The launch of fdf_orient_device / fdf_orient_points (arguments already validated).
+hipError_t orient_enqueue(const uint8_t* d_frames, uint32_t n_frames, uint32_t width,
+                          uint32_t height, uint64_t frame_stride, const fdf_point* d_points,
+                          uint64_t cap, const uint64_t* d_offsets, uint32_t radius,
+                          float* d_angles, int32_t* d_moments, hipStream_t s) {
+    fdfk::OrientParams p{};
+    p.frames = d_frames;
+    p.frame_stride = frame_stride;
+    p.pts = reinterpret_cast<const uint2*>(d_points);
+    p.offs = d_offsets;
+    p.cap = cap;
+    p.n_frames = n_frames;
+    p.width = width;
+    p.height = height;
+    p.radius = radius;
+    p.angles = d_angles;
+    p.moments = d_moments;
+    if (fdf_orient_disc(radius, p.u) != FDF_OK) return hipErrorInvalidValue;
+    // workgroups per frame: about 256 points each at the detector's usual density
+    const uint64_t est = std::min<uint64_t>(cap, (uint64_t)width * height / 32 * n_frames);
+    const uint32_t chunks = (uint32_t)std::min<uint64_t>(256, est / n_frames / 256 + 1);
+    return fdfk::launch_orient(p, chunks, s);
+}
+
+}  // namespace
+
+int fdf_orient_device(fdf_ctx* ctx, const uint8_t* d_frames, uint32_t n_frames, uint32_t width,
+                      uint32_t height, uint64_t frame_stride_bytes, const fdf_point* d_points,
+                      uint64_t cap, const uint64_t* d_frame_offsets, uint32_t radius,
+                      float* d_angles, int32_t* d_moments, void* stream) {
+    if (!ctx || !d_frame_offsets || radius == 0 || radius > fdfk::kOrientMaxRadius ||
+        n_frames > 65535u)
+        return FDF_ERR_ARG;
+    int empty = 0;
+    const int rc = check_shape(width, height, &empty);
+    if (rc) return rc;
+    if (empty || n_frames == 0 || cap == 0) return FDF_OK;
+    if (!d_frames || !d_points || !d_angles) return FDF_ERR_ARG;
+    if ((uint64_t)width * height > fdfk::kOrientMaxPixels) return FDF_ERR_SIZE;
+    if (n_frames > 1 && frame_stride_bytes < (uint64_t)width * height) return FDF_ERR_ARG;
+    DeviceGuard guard(ctx->device);
+    const uint64_t fs = n_frames > 1 ? frame_stride_bytes : (uint64_t)width * height;
+    return orient_enqueue(d_frames, n_frames, width, height, fs, d_points, cap, d_frame_offsets,
+                          radius, d_angles, d_moments,
+                          reinterpret_cast<hipStream_t>(stream)) == hipSuccess
+               ? FDF_OK
+               : FDF_ERR_DEVICE;
+}
+
+int fdf_orient_points(fdf_ctx* ctx, const uint8_t* data, uint32_t width, uint32_t height,
+                      size_t stride_bytes, const fdf_point* points, size_t n_points,
+                      uint32_t radius, float* out_angles, int32_t* out_moments) {
+    if (!ctx || radius == 0 || radius > fdfk::kOrientMaxRadius) return FDF_ERR_ARG;
+    if (n_points && (!points || !out_angles || !data)) return FDF_ERR_ARG;
+    if (stride_bytes < width) return FDF_ERR_ARG;
+    for (size_t k = 0; k < n_points; ++k)
+        if (points[k].x >= width || points[k].y >= height) return FDF_ERR_ARG;
+    if (n_points == 0) return FDF_OK;
+    const uint64_t frame_bytes = (uint64_t)width * height;
+    if (frame_bytes > fdfk::kOrientMaxPixels) return FDF_ERR_SIZE;
+    // one allocation for the call, cut into 256-byte aligned parts; the context's workspace
+    // and retained result (fdf_fetch_last) are not touched
+    const uint64_t o_pts = align256(frame_bytes);
+    const uint64_t o_offs = o_pts + align256(n_points * sizeof(fdf_point));
+    const uint64_t o_ang = o_offs + 256;
+    const uint64_t o_mom = o_ang + align256(n_points * sizeof(float));
+    const uint64_t bytes = o_mom + (out_moments ? align256(n_points * 2 * sizeof(int32_t)) : 0);
+    std::lock_guard<std::mutex> lock(ctx->mu);    // the context's stream carries the call
+    DeviceGuard guard(ctx->device);
+    uint8_t* d = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&d), bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return FDF_ERR_ALLOC;
+    }
+    const uint64_t one_frame[2] = {0, n_points};
+    hipStream_t s = ctx->stream;
+    hipError_t e = stride_bytes == width
+                       ? hipMemcpyAsync(d, data, frame_bytes, hipMemcpyHostToDevice, s)
+                       : hipMemcpy2DAsync(d, width, data, stride_bytes, width, height,
+                                          hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(d + o_pts, points, n_points * sizeof(fdf_point), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(d + o_offs, one_frame, sizeof(one_frame), hipMemcpyHostToDevice, s);
+    int32_t* d_mom = out_moments ? reinterpret_cast<int32_t*>(d + o_mom) : nullptr;
+    if (e == hipSuccess)
+        e = orient_enqueue(d, 1, width, height, frame_bytes,
+                           reinterpret_cast<const fdf_point*>(d + o_pts), n_points,
+                           reinterpret_cast<const uint64_t*>(d + o_offs), radius,
+                           reinterpret_cast<float*>(d + o_ang), d_mom, s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(out_angles, d + o_ang, n_points * sizeof(float), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && out_moments)
+        e = hipMemcpyAsync(out_moments, d_mom, n_points * 2 * sizeof(int32_t),
+                           hipMemcpyDeviceToHost, s);
+    const hipError_t se = hipStreamSynchronize(s);     // nothing may still use `d`
+    if (e == hipSuccess) e = se;
+    (void)hipFree(d);
+    return e == hipSuccess ? FDF_OK : FDF_ERR_DEVICE;
 }
 
 // ---- ring-level helpers (src/fast_simd.rs:69-110, :623, :722) ---------------------------

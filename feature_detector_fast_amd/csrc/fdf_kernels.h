@@ -1,6 +1,6 @@
 // fdf_kernels.h -- shared between the HIP kernels (fdf_sweep.hip, fdf_kernels.hip,
-// fdf_select.hip) and the C-ABI host layer (fdf_api.cpp): geometry constants, LDS layout and
-// launch parameters.
+// fdf_select.hip, fdf_orient.hip) and the C-ABI host layer (fdf_api.cpp): geometry constants,
+// LDS layout and launch parameters.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -281,5 +281,23 @@ struct SelectParams {
 };
 // select, scan and scatter kernels on `stream` (frame_tot already zeroed there)
 hipError_t launch_select(const SelectParams& p, hipStream_t stream);
+
+// Intensity-centroid orientation (fdf_orient.hip; fdf_orient_device).
+constexpr int kOrientThreads = 256;
+constexpr uint32_t kOrientMaxRadius = 31;             // window of 2 r + 1 <= 64 bytes
+constexpr uint64_t kOrientMaxPixels = 0x7fffff00ull;  // byte offsets of a frame fit an int
+struct OrientParams {
+    const uint8_t* frames;       // frame f at frames + f * frame_stride, width * height bytes
+    uint64_t frame_stride;
+    const uint2* pts;            // `cap` points, frames concatenated
+    const uint64_t* offs;        // n_frames + 1 entries
+    uint64_t cap;
+    uint32_t n_frames, width, height, radius;
+    float* angles;               // `cap` entries
+    int32_t* moments;            // 2 * `cap` entries (m10, m01), or NULL
+    uint8_t u[kOrientMaxRadius + 1];   // half-widths u[0..radius] of the disc (fdf_orient_disc)
+};
+// one kernel on `stream`: `chunks` workgroups per frame share the frame's points
+hipError_t launch_orient(const OrientParams& p, uint32_t chunks, hipStream_t stream);
 
 }  // namespace fdfk

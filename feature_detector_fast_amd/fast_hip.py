@@ -688,11 +688,106 @@ def detect_best_array(img, config, cell, k, device=0):
     return select_best(pts, scores, arr.shape, (cw, ch), k, device=device)
 
 
+def _radius(radius):
+    r = int(radius)
+    if not 1 <= r <= 31:
+        raise ValueError("radius must be in 1..31")
+    return r
+
+
+def orient_disc(radius):
+    """Half-widths u[0..radius] of the orientation disc (fdf_orient_disc; host only, no
+    device): row v spans the columns |d| <= u[|v|].  OpenCV's umax table."""
+    r = _radius(radius)
+    u = np.zeros(r + 1, dtype=np.uint8)
+    check(_native.load().fdf_orient_disc(r, u.ctypes.data), "fdf_orient_disc")
+    return u
+
+
+def orient_device(frames, points, offsets, angles, radius=15, moments=None, stream=None,
+                  device=None):
+    """Intensity-centroid angles of detect_device's (or select_device's) output, on the
+    device (fdf_orient_device): ``frames`` (F, H, W) uint8 with contiguous frames any number
+    of bytes apart, ``points`` (cap, 2) and ``offsets`` (F+1,) int64 as detect_device filled
+    them.  ``angles`` (cap,) float32 gets atan2(m01, m10) of the disc of ``radius`` around
+    every point, ``moments`` (optional, (cap, 2) int32) the exact (m10, m01).  Asynchronous on
+    ``stream`` (default: torch's current stream)."""
+    import torch
+
+    r = _radius(radius)
+    if frames.dim() != 3 or frames.dtype != torch.uint8 or \
+            (frames.numel() and (frames.stride(2) != 1 or frames.stride(1) != frames.shape[2]
+                                 or (frames.shape[0] > 1 and
+                                     frames.stride(0) < frames.shape[1] * frames.shape[2]))):
+        raise ValueError("frames must be a (F, H, W) uint8 tensor of contiguous frames")
+    if points.dim() != 2 or points.shape[1] != 2 or points.element_size() != 4 or \
+            not points.is_contiguous() or points.is_floating_point():
+        raise ValueError("points must be a contiguous (cap, 2) 32-bit integer tensor")
+    cap = points.shape[0]
+    if angles.dtype != torch.float32 or angles.dim() != 1 or angles.numel() < cap or \
+            not angles.is_contiguous():
+        raise ValueError("angles must be a contiguous float32 tensor with cap entries")
+    if moments is not None and (moments.dtype != torch.int32 or moments.dim() != 2 or
+                                moments.shape[1] != 2 or moments.shape[0] < cap or
+                                not moments.is_contiguous()):
+        raise ValueError("moments must be a contiguous (cap, 2) int32 tensor")
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or not offsets.is_contiguous() or \
+            offsets.numel() < frames.shape[0] + 1:
+        raise ValueError("offsets must be a contiguous int64 tensor with F+1 entries")
+    tensors = [frames, points, offsets, angles] + ([moments] if moments is not None else [])
+    if not all(t.is_cuda for t in tensors) or len({t.device for t in tensors}) != 1:
+        raise ValueError("orient_device needs CUDA (HIP) tensors on one device")
+    dev = frames.device.index if device is None else device
+    if stream is None:
+        stream = torch.cuda.current_stream(frames.device)
+    f, h, w = frames.shape
+    rc = _native.load().fdf_orient_device(
+        context(dev).handle, frames.data_ptr(), f, w, h, frames.stride(0) if f > 1 else h * w,
+        points.data_ptr(), cap, offsets.data_ptr(), r, angles.data_ptr(),
+        moments.data_ptr() if moments is not None else None,
+        ctypes.c_void_p(stream.cuda_stream))
+    check(rc, "fdf_orient_device")
+
+
+def keypoint_angles(img, points, radius=15, device=0, moments=False):
+    """Intensity-centroid angles ((K,) float32, radians in (-pi, pi], y down) of the given
+    ``points`` (K, 2) of one image (fdf_orient_points); with ``moments`` also the exact
+    (K, 2) int32 (m10, m01).  Points outside the image are an error."""
+    r = _radius(radius)
+    arr = _as_pixels(img)
+    pts = np.asarray(points)
+    if pts.ndim != 2 or pts.shape[1] != 2 or pts.dtype.kind not in "ui":
+        raise TypeError("points must be a (K, 2) integer array")
+    if pts.size and (pts.min() < 0 or pts.max() > 0xffffffff):
+        raise ValueError("points must fit u32")
+    pts = np.ascontiguousarray(pts, dtype=np.uint32)
+    h, w = arr.shape
+    n = pts.shape[0]
+    angles = np.zeros(n, dtype=np.float32)
+    mom = np.zeros((n, 2), dtype=np.int32) if moments else None
+    rc = _native.load().fdf_orient_points(
+        context(device).handle, arr.ctypes.data if arr.size else None, w, h,
+        arr.strides[0] if arr.size else w, pts.ctypes.data if n else None, n, r,
+        angles.ctypes.data if n else None, mom.ctypes.data if moments and n else None)
+    check(rc, "fdf_orient_points")
+    return (angles, mom) if moments else angles
+
+
+def detect_oriented_array(img, config, radius=15, device=0):
+    """detect_scored_array followed by keypoint_angles: ((K, 2) uint32 points in raster
+    order, (K,) uint16 scores, (K,) float32 angles)."""
+    r = _radius(radius)
+    arr = _as_pixels(img)
+    pts, scores = detect_scored_array(arr, config, device=device)
+    return pts, scores, keypoint_angles(arr, pts, r, device=device)
+
+
 __all__ = ["NORTH", "EAST", "SOUTH", "WEST", "circle", "calculate_offsets", "context",
            "shard_contexts", "capacity_guess", "Lanes",
            "detect_array", "detector", "detector_batch", "detect_device", "keypoint_scores",
            "detect_scored_array", "detector_scored", "detector_batch_scored", "score_device",
            "select_scratch_bytes", "select_device", "select_best", "detect_best_array",
+           "orient_disc", "orient_device", "keypoint_angles", "detect_oriented_array",
            "detect_rgb_array", "detector_rgb", "rgb_to_luma", "detect_device_rgb",
            "score_rings", "score_rings_device", "keypoint_score_max_threshold",
            "keypoint_score_sum_abs_difference", "NonMaximalSuppression"]

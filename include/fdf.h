@@ -32,7 +32,8 @@ extern "C" {
 #endif
 
 /* 6 still: fdf_select_scratch_bytes, fdf_select_device and fdf_select_points were added
- * without changing any existing function, which is backward compatible. */
+ * without changing any existing function, which is backward compatible; so were
+ * fdf_orient_disc, fdf_orient_device and fdf_orient_points. */
 #define FDF_ABI_VERSION 6
 
 /* Status codes.  Shapes the reference maps to an empty Vec return FDF_OK with 0 points. */
@@ -386,6 +387,59 @@ int fdf_select_points(fdf_ctx* ctx, const fdf_point* points, const uint16_t* sco
                       uint32_t width, uint32_t height, uint32_t cell_w, uint32_t cell_h,
                       uint32_t k, fdf_point* out, uint16_t* out_scores, size_t cap,
                       uint64_t* out_offsets, size_t* n_out);
+
+/*
+ * Keypoint orientation by intensity centroid (extension: the reference returns points only;
+ * this is the angle of oFAST / ORB, OpenCV's IC_Angle).
+ *
+ * Disc.  radius r, 1 <= r <= 31 (ORB's patch of 31 is r = 15).  Row v of the disc, |v| <= r,
+ * spans the columns |d| <= u[|v|], with the half-widths u[0..r] of OpenCV's umax rule:
+ * vmax = floor(r * sqrt(2) / 2 + 1), vmin = ceil(r * sqrt(2) / 2); u[v] =
+ * floor(sqrt(r^2 - v^2) + 0.5) for v in 0..vmax; then with v0 = 0, for v from r down to vmin:
+ * advance v0 while u[v0] == u[v0 + 1], set u[v] = v0, then v0++.  r = 15 gives
+ * 15,15,15,15,14,14,14,13,13,12,11,10,9,8,6,3 (749 pixels).
+ *
+ * Moments, exact in int32: for the keypoint (x, y) of a frame
+ *   m10 = sum over v, |d| <= u[|v|] of d * I(x + d, y + v)
+ *   m01 = sum over v, |d| <= u[|v|] of v * I(x + d, y + v)
+ * where I(cx, cy) is the pixel at (clamp(cx, 0, width - 1), clamp(cy, 0, height - 1)): a
+ * replicated border; the weights d and v are not clamped.  |m| < 2^24 for every r <= 31, so
+ * the conversion to float is exact.  For keypoints at least r pixels inside the frame these
+ * are OpenCV's moments; a caller who wants its edgeThreshold filters the others.
+ *
+ * Angle = atan2f((float)m01, (float)m10), radians in (-pi, pi], y pointing down;
+ * m10 = m01 = 0 gives exactly 0.0f.
+ *
+ * fdf_orient_disc: host only, no context; writes u[0..radius] (radius + 1 entries).
+ * FDF_ERR_ARG for radius 0, radius > 31 or a NULL pointer.
+ *
+ * fdf_orient_device: the inputs are what fdf_detect_device (or fdf_select_device) leaves on
+ * the device: frame f owns the indices [offs[f], min(offs[f+1], cap)) and its pixels start at
+ * d_frames + f * frame_stride_bytes (any alignment).  d_angles gets `cap` floats, d_moments
+ * (optional) 2 int32 per point, m10 then m01; entries at index >= min(offs[n_frames], cap)
+ * are not written.  Asynchronous on `stream` (NULL = the HIP null stream); like
+ * fdf_score_device it takes no context lock and uses no context workspace, it only binds the
+ * context's device; nothing is allocated and nothing returns to the host.  FDF_ERR_ARG,
+ * synchronously and with nothing launched: a bad radius, a NULL required pointer,
+ * n_frames > 65535, a frame stride below width * height when n_frames > 1.  Shape errors and
+ * empty shapes as for fdf_score_device (FDF_OK, nothing written); width * height above
+ * 2^31 - 256 is FDF_ERR_SIZE.  A point with x >= width or y >= height gives an unspecified
+ * value for that point.  Whatever the points hold, no access leaves
+ * [d_frames, d_frames + (n_frames - 1) * stride + width * height) or the other buffers.
+ *
+ * fdf_orient_points: one host frame (rows stride_bytes apart) and host points, synchronous.
+ * Points outside the image are rejected with FDF_ERR_ARG.  Copies through device buffers
+ * allocated and freed by the call and runs the same kernel; the context's workspace and
+ * retained result are untouched, so fdf_fetch_last stays valid.  out_moments may be NULL.
+ */
+int fdf_orient_disc(uint32_t radius, uint8_t* half_widths);
+int fdf_orient_device(fdf_ctx* ctx, const uint8_t* d_frames, uint32_t n_frames, uint32_t width,
+                      uint32_t height, uint64_t frame_stride_bytes, const fdf_point* d_points,
+                      uint64_t cap, const uint64_t* d_frame_offsets, uint32_t radius,
+                      float* d_angles, int32_t* d_moments, void* stream);
+int fdf_orient_points(fdf_ctx* ctx, const uint8_t* data, uint32_t width, uint32_t height,
+                      size_t stride_bytes, const fdf_point* points, size_t n_points,
+                      uint32_t radius, float* out_angles, int32_t* out_moments);
 
 /*
  * Streaming host pipeline (extension; the reference's callers detect on one

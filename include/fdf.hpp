@@ -15,6 +15,7 @@
 //   keypoint_score_sum_abs_difference :722               fdf::fast_hip::keypoint_score_sum_abs_difference
 //   image::GrayImage                (image 0.24.6)       fdf::GrayView (borrowed row-major u8)
 //   (none: callers keep the best K)  --                   fdf::select_best(points, scores, ...)
+//   (none: ORB-style callers orient) --                   fdf::keypoint_angles(img, points, ...)
 //
 // Where the reference panics (n < 9, n > 16, degenerate sizes) these throw fdf::Error.
 // Each thread lazily owns one device context per HIP device (device 0 unless
@@ -215,6 +216,26 @@ inline std::pair<std::vector<Point>, std::vector<uint16_t>> select_best(
     const std::vector<Point>& points, const std::vector<uint16_t>& scores, uint32_t width,
     uint32_t height, uint32_t cell_w, uint32_t cell_h, uint32_t k) {
     return select_best(points, scores, width, height, cell_w, cell_h, k, thread_context());
+}
+
+// Orientation by intensity centroid (extension, fdf_orient_points): atan2f(m01, m10) of the
+// disc of `radius` (1..31; ORB's is 15) around every point of one image, radians in
+// (-pi, pi] with y pointing down; `moments` (optional) gets m10, m01 per point.
+inline std::vector<float> keypoint_angles(const GrayView& img, const std::vector<Point>& points,
+                                          uint32_t radius, Context& ctx,
+                                          std::vector<int32_t>* moments = nullptr) {
+    std::vector<float> angles(points.size());
+    if (moments) moments->assign(2 * points.size(), 0);
+    check(fdf_orient_points(ctx.get(), img.data, img.width, img.height, img.stride,
+                            reinterpret_cast<const fdf_point*>(points.data()), points.size(),
+                            radius, angles.data(), moments ? moments->data() : nullptr),
+          "fdf_orient_points");
+    return angles;
+}
+inline std::vector<float> keypoint_angles(const GrayView& img, const std::vector<Point>& points,
+                                          uint32_t radius = 15,
+                                          std::vector<int32_t>* moments = nullptr) {
+    return keypoint_angles(img, points, radius, thread_context(), moments);
 }
 
 inline std::vector<Point> detect(const GrayView& img, const Config& config) {
