@@ -42,7 +42,8 @@ EXPORTED_SYMBOLS = (
     "fdf_score_rings_device", "fdf_ctx_set_band_rows", "fdf_ctx_set_upload_chunks",
     "fdf_ctx_recoveries", "fdf_ctx_test_skew_tickets", "fdf_select_scratch_bytes",
     "fdf_select_device", "fdf_select_points", "fdf_orient_disc", "fdf_orient_device",
-    "fdf_orient_points",
+    "fdf_orient_points", "fdf_brief_pattern", "fdf_brief_steer", "fdf_smooth_device",
+    "fdf_describe_device", "fdf_describe_points",
 )
 
 
@@ -195,6 +196,18 @@ def load():
     lib.fdf_orient_device.argtypes = [vp, vp, u32, u32, u32, u64, vp, u64, vp, u32, vp, vp, vp]
     lib.fdf_orient_points.restype = ctypes.c_int
     lib.fdf_orient_points.argtypes = [vp, vp, u32, u32, sz, vp, sz, u32, vp, vp]
+    lib.fdf_brief_pattern.restype = ctypes.c_int
+    lib.fdf_brief_pattern.argtypes = [vp]
+    lib.fdf_brief_steer.restype = ctypes.c_int
+    lib.fdf_brief_steer.argtypes = [vp, u32, vp]
+    lib.fdf_smooth_device.restype = ctypes.c_int
+    lib.fdf_smooth_device.argtypes = [vp, vp, u32, u32, u32, u64, vp, u64, vp]
+    lib.fdf_describe_device.restype = ctypes.c_int
+    lib.fdf_describe_device.argtypes = [vp, vp, u32, u32, u32, u64, vp, u64, vp, vp, vp, u32, vp,
+                                        vp]
+    lib.fdf_describe_points.restype = ctypes.c_int
+    lib.fdf_describe_points.argtypes = [vp, vp, u32, u32, sz, vp, sz, vp, vp, u32, ctypes.c_int,
+                                        vp]
     del u8p
     _lib = lib
     return lib

@@ -1753,6 +1753,223 @@ int fdf_orient_points(fdf_ctx* ctx, const uint8_t* data, uint32_t width, uint32_
     return e == hipSuccess ? FDF_OK : FDF_ERR_DEVICE;
 }
 
+// ---- steered BRIEF descriptors and box smoothing (fdf_describe.hip) -----------------------
+
+int fdf_brief_pattern(int8_t pattern[1024]) {
+    if (!pattern) return FDF_ERR_ARG;
+    uint32_t s = 0x9E3779B9u;
+    auto next = [&s]() {
+        s ^= s << 13;
+        s ^= s >> 17;
+        s ^= s << 5;
+        return s;
+    };
+    auto coord = [&next]() {              // bell-shaped in -21..21
+        int v = -21;
+        for (int k = 0; k < 6; ++k) v += (int)(next() >> 29);
+        return v;
+    };
+    uint32_t n = 0;
+    while (n < fdfk::kBriefTests) {
+        int t[4];
+        for (int& v : t) v = coord();
+        if (t[0] * t[0] + t[1] * t[1] > 13 * 13 || t[2] * t[2] + t[3] * t[3] > 13 * 13) continue;
+        if (t[0] == t[2] && t[1] == t[3]) continue;
+        bool seen = false;
+        for (uint32_t k = 0; k < n && !seen; ++k)
+            seen = pattern[4 * k] == t[0] && pattern[4 * k + 1] == t[1] &&
+                   pattern[4 * k + 2] == t[2] && pattern[4 * k + 3] == t[3];
+        if (seen) continue;
+        for (int k = 0; k < 4; ++k) pattern[4 * n + k] = (int8_t)t[k];
+        ++n;
+    }
+    return FDF_OK;
+}
+
+int fdf_brief_steer(const int8_t* pattern, uint32_t n_bins, int8_t* table) {
+#pragma clang fp contract(off)
+    if (!pattern || !table || n_bins == 0 || n_bins > fdfk::kBriefMaxBins) return FDF_ERR_ARG;
+    // double products and sums, one rounding to float, then half away from zero
+    auto quantise = [](double v) {
+        const float r = std::round((float)v);
+        return (int8_t)std::min(std::max(r, -128.0f), 127.0f);
+    };
+    for (uint32_t b = 0; b < n_bins; ++b) {
+        const double theta = 2 * M_PI * b / n_bins;
+        const double c = std::cos(theta), s = std::sin(theta);
+        int8_t* row = table + (size_t)b * fdfk::kBriefTableBytes;
+        for (uint32_t k = 0; k < 2 * fdfk::kBriefTests; ++k) {    // points (x, y), y pointing down
+            const double x = pattern[2 * k], y = pattern[2 * k + 1];
+            const double xc = x * c, ys = y * s, xs = x * s, yc = y * c;
+            row[2 * k] = quantise(xc - ys);
+            row[2 * k + 1] = quantise(xs + yc);
+        }
+    }
+    return FDF_OK;
+}
+
+namespace {
+
+hipError_t smooth_enqueue(const uint8_t* d_frames, uint32_t n_frames, uint32_t width,
+                          uint32_t height, uint64_t frame_stride, uint8_t* d_out,
+                          uint64_t out_stride, hipStream_t s) {
+    fdfk::SmoothParams p{};
+    p.frames = d_frames;
+    p.frame_stride = frame_stride;
+    p.out = d_out;
+    p.out_stride = out_stride;
+    p.n_frames = n_frames;
+    p.width = width;
+    p.height = height;
+    p.groups = (width + 3) / 4;
+    // the tallest strips (4 halo rows read per strip) that still leave 16 waves per CU
+    p.strip_rows = fdfk::kSmoothStripRows;
+    while (p.strip_rows > 8 &&
+           (uint64_t)p.groups * ((height + p.strip_rows - 1) / p.strip_rows) * n_frames < 256 * 1024)
+        p.strip_rows /= 2;
+    p.strips = (height + p.strip_rows - 1) / p.strip_rows;
+    return fdfk::launch_smooth(p, s);
+}
+
+// The launch of fdf_describe_device / fdf_describe_points (arguments already validated).
+hipError_t describe_enqueue(const uint8_t* d_frames, uint32_t n_frames, uint32_t width,
+                            uint32_t height, uint64_t frame_stride, const fdf_point* d_points,
+                            uint64_t cap, const uint64_t* d_offsets, const float* d_angles,
+                            const int8_t* d_table, uint32_t n_bins, uint8_t* d_desc,
+                            hipStream_t s) {
+    fdfk::DescribeParams p{};
+    p.frames = d_frames;
+    p.frame_stride = frame_stride;
+    p.pts = reinterpret_cast<const uint2*>(d_points);
+    p.offs = d_offsets;
+    p.cap = cap;
+    p.n_frames = n_frames;
+    p.width = width;
+    p.height = height;
+    p.angles = d_angles;
+    p.table = d_table;
+    p.n_bins = n_bins;
+    p.scale = (float)(n_bins / (2 * M_PI));
+    p.desc = d_desc;
+    // workgroups per frame: about 64 points each at the detector's usual density
+    const uint64_t est = std::min<uint64_t>(cap, (uint64_t)width * height / 32 * n_frames);
+    const uint32_t chunks = (uint32_t)std::min<uint64_t>(1024, est / n_frames / 64 + 1);
+    return fdfk::launch_describe(p, chunks, s);
+}
+
+}  // namespace
+
+int fdf_smooth_device(fdf_ctx* ctx, const uint8_t* d_frames, uint32_t n_frames, uint32_t width,
+                      uint32_t height, uint64_t frame_stride_bytes, uint8_t* d_out,
+                      uint64_t out_frame_stride_bytes, void* stream) {
+    if (!ctx || n_frames > 65535u) return FDF_ERR_ARG;
+    if (width == 0 || height == 0 || (uint64_t)width * height > fdfk::kOrientMaxPixels)
+        return FDF_ERR_SIZE;
+    if (n_frames == 0) return FDF_OK;
+    if (!d_frames || !d_out) return FDF_ERR_ARG;
+    const uint64_t frame_bytes = (uint64_t)width * height;
+    if (n_frames > 1 && (frame_stride_bytes < frame_bytes || out_frame_stride_bytes < frame_bytes))
+        return FDF_ERR_ARG;
+    DeviceGuard guard(ctx->device);
+    return smooth_enqueue(d_frames, n_frames, width, height,
+                          n_frames > 1 ? frame_stride_bytes : frame_bytes, d_out,
+                          n_frames > 1 ? out_frame_stride_bytes : frame_bytes,
+                          reinterpret_cast<hipStream_t>(stream)) == hipSuccess
+               ? FDF_OK
+               : FDF_ERR_DEVICE;
+}
+
+int fdf_describe_device(fdf_ctx* ctx, const uint8_t* d_frames, uint32_t n_frames, uint32_t width,
+                        uint32_t height, uint64_t frame_stride_bytes, const fdf_point* d_points,
+                        uint64_t cap, const uint64_t* d_frame_offsets, const float* d_angles,
+                        const int8_t* d_table, uint32_t n_bins, uint8_t* d_desc, void* stream) {
+    if (!ctx || !d_frame_offsets || !d_table || n_bins == 0 || n_bins > fdfk::kBriefMaxBins ||
+        n_frames > 65535u)
+        return FDF_ERR_ARG;
+    int empty = 0;
+    const int rc = check_shape(width, height, &empty);
+    if (rc) return rc;
+    if (empty || n_frames == 0 || cap == 0) return FDF_OK;
+    if (!d_frames || !d_points || !d_desc) return FDF_ERR_ARG;
+    if ((uint64_t)width * height > fdfk::kOrientMaxPixels) return FDF_ERR_SIZE;
+    if (n_frames > 1 && frame_stride_bytes < (uint64_t)width * height) return FDF_ERR_ARG;
+    DeviceGuard guard(ctx->device);
+    const uint64_t fs = n_frames > 1 ? frame_stride_bytes : (uint64_t)width * height;
+    return describe_enqueue(d_frames, n_frames, width, height, fs, d_points, cap, d_frame_offsets,
+                            d_angles, d_table, n_bins, d_desc,
+                            reinterpret_cast<hipStream_t>(stream)) == hipSuccess
+               ? FDF_OK
+               : FDF_ERR_DEVICE;
+}
+
+int fdf_describe_points(fdf_ctx* ctx, const uint8_t* data, uint32_t width, uint32_t height,
+                        size_t stride_bytes, const fdf_point* points, size_t n_points,
+                        const float* angles, const int8_t* pattern, uint32_t n_bins, int smooth,
+                        uint8_t* out_desc) {
+    if (!ctx || n_bins == 0 || n_bins > fdfk::kBriefMaxBins || (smooth != 0 && smooth != 1))
+        return FDF_ERR_ARG;
+    if (n_points && (!points || !out_desc || !data)) return FDF_ERR_ARG;
+    if (stride_bytes < width) return FDF_ERR_ARG;
+    for (size_t k = 0; k < n_points; ++k)
+        if (points[k].x >= width || points[k].y >= height) return FDF_ERR_ARG;
+    if (n_points == 0) return FDF_OK;
+    const uint64_t frame_bytes = (uint64_t)width * height;
+    if (frame_bytes > fdfk::kOrientMaxPixels) return FDF_ERR_SIZE;
+    int8_t default_pattern[fdfk::kBriefTableBytes];
+    if (!pattern) {
+        fdf_brief_pattern(default_pattern);
+        pattern = default_pattern;
+    }
+    const uint64_t table_bytes = (uint64_t)n_bins * fdfk::kBriefTableBytes;
+    std::vector<int8_t> table(table_bytes);
+    if (fdf_brief_steer(pattern, n_bins, table.data()) != FDF_OK) return FDF_ERR_ARG;
+    // one allocation for the call, cut into 256-byte aligned parts; the context's workspace
+    // and retained result (fdf_fetch_last) are not touched
+    const uint64_t o_smooth = align256(frame_bytes);
+    const uint64_t o_pts = o_smooth + (smooth ? align256(frame_bytes) : 0);
+    const uint64_t o_offs = o_pts + align256(n_points * sizeof(fdf_point));
+    const uint64_t o_ang = o_offs + 256;
+    const uint64_t o_table = o_ang + (angles ? align256(n_points * sizeof(float)) : 0);
+    const uint64_t o_desc = o_table + align256(table_bytes);
+    const uint64_t bytes = o_desc + align256(n_points * (uint64_t)fdfk::kBriefBytes);
+    std::lock_guard<std::mutex> lock(ctx->mu);    // the context's stream carries the call
+    DeviceGuard guard(ctx->device);
+    uint8_t* d = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&d), bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return FDF_ERR_ALLOC;
+    }
+    const uint64_t one_frame[2] = {0, n_points};
+    hipStream_t s = ctx->stream;
+    hipError_t e = stride_bytes == width
+                       ? hipMemcpyAsync(d, data, frame_bytes, hipMemcpyHostToDevice, s)
+                       : hipMemcpy2DAsync(d, width, data, stride_bytes, width, height,
+                                          hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(d + o_pts, points, n_points * sizeof(fdf_point), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(d + o_offs, one_frame, sizeof(one_frame), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && angles)
+        e = hipMemcpyAsync(d + o_ang, angles, n_points * sizeof(float), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(d + o_table, table.data(), table_bytes, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && smooth)
+        e = smooth_enqueue(d, 1, width, height, frame_bytes, d + o_smooth, frame_bytes, s);
+    if (e == hipSuccess)
+        e = describe_enqueue(smooth ? d + o_smooth : d, 1, width, height, frame_bytes,
+                             reinterpret_cast<const fdf_point*>(d + o_pts), n_points,
+                             reinterpret_cast<const uint64_t*>(d + o_offs),
+                             angles ? reinterpret_cast<const float*>(d + o_ang) : nullptr,
+                             reinterpret_cast<const int8_t*>(d + o_table), n_bins, d + o_desc, s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(out_desc, d + o_desc, n_points * (uint64_t)fdfk::kBriefBytes,
+                           hipMemcpyDeviceToHost, s);
+    const hipError_t se = hipStreamSynchronize(s);     // nothing may still use `d`
+    if (e == hipSuccess) e = se;
+    (void)hipFree(d);
+    return e == hipSuccess ? FDF_OK : FDF_ERR_DEVICE;
+}
+
 // ---- ring-level helpers (src/fast_simd.rs:69-110, :623, :722) ---------------------------
 
 static constexpr int32_t kCircleDx[16] = {0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1};

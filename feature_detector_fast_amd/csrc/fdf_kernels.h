@@ -1,6 +1,6 @@
 // fdf_kernels.h -- shared between the HIP kernels (fdf_sweep.hip, fdf_kernels.hip,
-// fdf_select.hip, fdf_orient.hip) and the C-ABI host layer (fdf_api.cpp): geometry constants,
-// LDS layout and launch parameters.
+// fdf_select.hip, fdf_orient.hip, fdf_describe.hip) and the C-ABI host layer (fdf_api.cpp):
+// geometry constants, LDS layout and launch parameters.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -299,5 +299,46 @@ struct OrientParams {
 };
 // one kernel on `stream`: `chunks` workgroups per frame share the frame's points
 hipError_t launch_orient(const OrientParams& p, uint32_t chunks, hipStream_t stream);
+
+// Steered BRIEF descriptors and 5x5 box smoothing (fdf_describe.hip; fdf_describe_device,
+// fdf_smooth_device).
+constexpr int kDescribeThreads = 256;                 // 4 waves, one keypoint each per pass
+constexpr uint32_t kBriefTests = 256;
+constexpr uint32_t kBriefBytes = kBriefTests / 8;     // descriptor bytes per keypoint
+constexpr uint32_t kBriefTableBytes = kBriefTests * 4;   // one bin: (x0, y0, x1, y1) int8 per test
+constexpr uint32_t kBriefMaxBins = 360;
+struct DescribeParams {
+    const uint8_t* frames;       // frame f at frames + f * frame_stride, width * height bytes
+    uint64_t frame_stride;
+    const uint2* pts;            // `cap` points, frames concatenated
+    const uint64_t* offs;        // n_frames + 1 entries
+    uint64_t cap;
+    uint32_t n_frames, width, height;
+    const float* angles;         // `cap` entries, or NULL (bin 0)
+    const int8_t* table;         // n_bins * kBriefTableBytes (fdf_brief_steer)
+    uint32_t n_bins;
+    float scale;                 // (float)(n_bins / (2 pi))
+    uint8_t* desc;               // `cap` * kBriefBytes
+};
+// one kernel on `stream`: `chunks` workgroups per frame share the frame's points
+hipError_t launch_describe(const DescribeParams& p, uint32_t chunks, hipStream_t stream);
+
+constexpr int kSmoothThreads = 256;
+constexpr uint32_t kSmoothMinWidth = 8;              // narrower frames: a thread per pixel
+// Rows a thread walks when the grid is large enough (4 halo rows are read per strip).
+#ifndef FDF_SMOOTH_STRIP
+#define FDF_SMOOTH_STRIP 64
+#endif
+constexpr uint32_t kSmoothStripRows = FDF_SMOOTH_STRIP;
+struct SmoothParams {
+    const uint8_t* frames;       // frame f at frames + f * frame_stride, width * height bytes
+    uint64_t frame_stride;
+    uint8_t* out;                // frame f at out + f * out_stride
+    uint64_t out_stride;
+    uint32_t n_frames, width, height;
+    uint32_t groups;             // ceil(width / 4): a thread owns 4 columns
+    uint32_t strip_rows, strips; // rows a thread walks; strips = ceil(height / strip_rows)
+};
+hipError_t launch_smooth(const SmoothParams& p, hipStream_t stream);
 
 }  // namespace fdfk

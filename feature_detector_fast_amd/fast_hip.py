@@ -782,12 +782,177 @@ def detect_oriented_array(img, config, radius=15, device=0):
     return pts, scores, keypoint_angles(arr, pts, r, device=device)
 
 
+def _n_bins(n_bins):
+    n = int(n_bins)
+    if not 1 <= n <= 360:
+        raise ValueError("n_bins must be in 1..360")
+    return n
+
+
+def _pattern(pattern):
+    p = np.asarray(pattern)
+    if p.dtype != np.int8 or p.size != 1024 or p.shape not in ((256, 4), (1024,)):
+        raise TypeError("pattern must be a (256, 4) int8 array")
+    return np.ascontiguousarray(p).reshape(256, 4)
+
+
+def brief_pattern():
+    """The default BRIEF pattern (fdf_brief_pattern; host only, no device): (256, 4) int8,
+    test i = (x0, y0, x1, y1)."""
+    p = np.zeros((256, 4), dtype=np.int8)
+    check(_native.load().fdf_brief_pattern(p.ctypes.data), "fdf_brief_pattern")
+    return p
+
+
+def brief_steer(pattern, n_bins):
+    """The steering table of ``pattern`` ((256, 4) int8) for ``n_bins`` orientation bins
+    (fdf_brief_steer; host only, no device): (n_bins, 256, 4) int8, bin b = the pattern rotated
+    by 2 pi b / n_bins with y pointing down."""
+    n = _n_bins(n_bins)
+    p = _pattern(pattern)
+    table = np.zeros((n, 256, 4), dtype=np.int8)
+    check(_native.load().fdf_brief_steer(p.ctypes.data, n, table.ctypes.data), "fdf_brief_steer")
+    return table
+
+
+def _is_frames(torch, t):
+    """(F, H, W) uint8 with contiguous frames any number of bytes apart."""
+    return t.dim() == 3 and t.dtype == torch.uint8 and not (
+        t.numel() and (t.stride(2) != 1 or t.stride(1) != t.shape[2] or
+                       (t.shape[0] > 1 and t.stride(0) < t.shape[1] * t.shape[2])))
+
+
+def smooth_device(frames, out, stream=None, device=None):
+    """5 x 5 box smoothing on the device (fdf_smooth_device): ``out`` = (sum of the 5 x 5
+    neighbourhood at clamped coordinates + 12) // 25.  ``frames`` and ``out`` are (F, H, W)
+    uint8 tensors of the same shape with contiguous frames any number of bytes apart (each its
+    own); the bytes between output frames are not written.  They must not overlap.
+    Asynchronous on ``stream`` (default: torch's current stream)."""
+    import torch
+
+    for name, t in (("frames", frames), ("out", out)):
+        if not _is_frames(torch, t):
+            raise ValueError(f"{name} must be a (F, H, W) uint8 tensor of contiguous frames")
+    if frames.shape != out.shape:
+        raise ValueError("frames and out must have the same shape")
+    f, h, w = frames.shape
+    if f > 65535 or h < 1 or w < 1 or h * w > 0x7fffff00:
+        raise ValueError("at most 65535 frames of 1 <= width * height <= 2^31 - 256 pixels")
+    if not (frames.is_cuda and out.is_cuda) or frames.device != out.device:
+        raise ValueError("smooth_device needs CUDA (HIP) tensors on one device")
+    if f:
+        span = lambda t: (t.data_ptr(), t.data_ptr() + (f - 1) * t.stride(0) + h * w)
+        (a0, a1), (b0, b1) = span(frames), span(out)
+        if a0 < b1 and b0 < a1:
+            raise ValueError("frames and out must not overlap")
+    dev = frames.device.index if device is None else device
+    if stream is None:
+        stream = torch.cuda.current_stream(frames.device)
+    rc = _native.load().fdf_smooth_device(
+        context(dev).handle, frames.data_ptr(), f, w, h, frames.stride(0) if f > 1 else h * w,
+        out.data_ptr(), out.stride(0) if f > 1 else h * w, ctypes.c_void_p(stream.cuda_stream))
+    check(rc, "fdf_smooth_device")
+
+
+def describe_device(frames, points, offsets, desc, table, n_bins, angles=None, stream=None,
+                    device=None):
+    """Steered BRIEF descriptors of detect_device's (or select_device's) output, on the
+    device (fdf_describe_device): ``frames`` (F, H, W) uint8 with contiguous frames any number
+    of bytes apart (smoothed by smooth_device, or not: the caller's choice), ``points``
+    (cap, 2) and ``offsets`` (F+1,) int64 as detect_device filled them, ``angles`` (optional,
+    (cap,) float32) as orient_device filled them, ``table`` the int8 CUDA tensor of
+    brief_steer(pattern, n_bins).  ``desc`` (cap, 32) uint8 gets the 256 bits of every point,
+    test i in bit i % 8 of byte i // 8.  Without ``angles`` every point uses bin 0.
+    Asynchronous on ``stream`` (default: torch's current stream)."""
+    import torch
+
+    n = _n_bins(n_bins)
+    if not _is_frames(torch, frames):
+        raise ValueError("frames must be a (F, H, W) uint8 tensor of contiguous frames")
+    if points.dim() != 2 or points.shape[1] != 2 or points.element_size() != 4 or \
+            not points.is_contiguous() or points.is_floating_point():
+        raise ValueError("points must be a contiguous (cap, 2) 32-bit integer tensor")
+    cap = points.shape[0]
+    if desc.dtype != torch.uint8 or desc.dim() != 2 or desc.shape[1] != 32 or \
+            desc.shape[0] < cap or not desc.is_contiguous():
+        raise ValueError("desc must be a contiguous (cap, 32) uint8 tensor")
+    if table.dtype != torch.int8 or not table.is_contiguous() or table.numel() != n * 1024:
+        raise ValueError("table must be a contiguous int8 tensor of n_bins * 256 * 4 entries")
+    if angles is not None and (angles.dtype != torch.float32 or angles.dim() != 1 or
+                               angles.numel() < cap or not angles.is_contiguous()):
+        raise ValueError("angles must be a contiguous float32 tensor with cap entries")
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or not offsets.is_contiguous() or \
+            offsets.numel() < frames.shape[0] + 1:
+        raise ValueError("offsets must be a contiguous int64 tensor with F+1 entries")
+    tensors = [frames, points, offsets, desc, table] + ([angles] if angles is not None else [])
+    if not all(t.is_cuda for t in tensors) or len({t.device for t in tensors}) != 1:
+        raise ValueError("describe_device needs CUDA (HIP) tensors on one device")
+    dev = frames.device.index if device is None else device
+    if stream is None:
+        stream = torch.cuda.current_stream(frames.device)
+    f, h, w = frames.shape
+    rc = _native.load().fdf_describe_device(
+        context(dev).handle, frames.data_ptr(), f, w, h, frames.stride(0) if f > 1 else h * w,
+        points.data_ptr(), cap, offsets.data_ptr(),
+        angles.data_ptr() if angles is not None else None, table.data_ptr(), n,
+        desc.data_ptr(), ctypes.c_void_p(stream.cuda_stream))
+    check(rc, "fdf_describe_device")
+
+
+def keypoint_descriptors(img, points, angles=None, pattern=None, n_bins=30, smooth=True,
+                         device=0):
+    """Steered BRIEF descriptors ((K, 32) uint8) of the given ``points`` (K, 2) of one image
+    (fdf_describe_points): ``angles`` (optional, (K,) float32 radians, as keypoint_angles
+    returns them) pick one of ``n_bins`` rotations of ``pattern`` ((256, 4) int8; None: the
+    default of brief_pattern); with ``smooth`` the tests read the 5 x 5 box-smoothed image.
+    Points outside the image are an error."""
+    n = _n_bins(n_bins)
+    arr = _as_pixels(img)
+    pts = np.asarray(points)
+    if pts.ndim != 2 or pts.shape[1] != 2 or pts.dtype.kind not in "ui":
+        raise TypeError("points must be a (K, 2) integer array")
+    if pts.size and (pts.min() < 0 or pts.max() > 0xffffffff):
+        raise ValueError("points must fit u32")
+    pts = np.ascontiguousarray(pts, dtype=np.uint32)
+    k = pts.shape[0]
+    if angles is not None:
+        ang = np.asarray(angles)
+        if ang.dtype != np.float32 or ang.shape != (k,):
+            raise TypeError("angles must be a (K,) float32 array, one per point")
+        ang = np.ascontiguousarray(ang)
+    pat = _pattern(pattern) if pattern is not None else None
+    h, w = arr.shape
+    desc = np.zeros((k, 32), dtype=np.uint8)
+    rc = _native.load().fdf_describe_points(
+        context(device).handle, arr.ctypes.data if arr.size else None, w, h,
+        arr.strides[0] if arr.size else w, pts.ctypes.data if k else None, k,
+        ang.ctypes.data if angles is not None and k else None,
+        pat.ctypes.data if pat is not None else None, n, 1 if smooth else 0,
+        desc.ctypes.data if k else None)
+    check(rc, "fdf_describe_points")
+    return desc
+
+
+def detect_described_array(img, config, radius=15, n_bins=30, device=0):
+    """detect_array, keypoint_angles on the image and keypoint_descriptors (default pattern)
+    on its smoothed copy: ((K, 2) uint32 points in raster order, (K,) float32 angles,
+    (K, 32) uint8 descriptors)."""
+    r = _radius(radius)
+    n = _n_bins(n_bins)
+    arr = _as_pixels(img)
+    pts = detect_array(arr, config, device=device)
+    angles = keypoint_angles(arr, pts, r, device=device)
+    return pts, angles, keypoint_descriptors(arr, pts, angles, n_bins=n, device=device)
+
+
 __all__ = ["NORTH", "EAST", "SOUTH", "WEST", "circle", "calculate_offsets", "context",
            "shard_contexts", "capacity_guess", "Lanes",
            "detect_array", "detector", "detector_batch", "detect_device", "keypoint_scores",
            "detect_scored_array", "detector_scored", "detector_batch_scored", "score_device",
            "select_scratch_bytes", "select_device", "select_best", "detect_best_array",
            "orient_disc", "orient_device", "keypoint_angles", "detect_oriented_array",
+           "brief_pattern", "brief_steer", "smooth_device", "describe_device",
+           "keypoint_descriptors", "detect_described_array",
            "detect_rgb_array", "detector_rgb", "rgb_to_luma", "detect_device_rgb",
            "score_rings", "score_rings_device", "keypoint_score_max_threshold",
            "keypoint_score_sum_abs_difference", "NonMaximalSuppression"]

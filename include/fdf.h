@@ -33,7 +33,8 @@ extern "C" {
 
 /* 6 still: fdf_select_scratch_bytes, fdf_select_device and fdf_select_points were added
  * without changing any existing function, which is backward compatible; so were
- * fdf_orient_disc, fdf_orient_device and fdf_orient_points. */
+ * fdf_orient_disc, fdf_orient_device and fdf_orient_points, and fdf_brief_pattern,
+ * fdf_brief_steer, fdf_smooth_device, fdf_describe_device and fdf_describe_points. */
 #define FDF_ABI_VERSION 6
 
 /* Status codes.  Shapes the reference maps to an empty Vec return FDF_OK with 0 points. */
@@ -440,6 +441,77 @@ int fdf_orient_device(fdf_ctx* ctx, const uint8_t* d_frames, uint32_t n_frames, 
 int fdf_orient_points(fdf_ctx* ctx, const uint8_t* data, uint32_t width, uint32_t height,
                       size_t stride_bytes, const fdf_point* points, size_t n_points,
                       uint32_t radius, float* out_angles, int32_t* out_moments);
+
+/*
+ * Steered BRIEF descriptors (extension: the reference returns points only; this is the rBRIEF
+ * of ORB, the step after fdf_orient_device) and the 5 x 5 box smoothing BRIEF is usually run
+ * on.  Everything is integer-exact.
+ *
+ * Pattern.  256 tests; test i is four int8 (x0, y0, x1, y1), 1024 bytes in all.  A caller who
+ * owns OpenCV's learned ORB table passes that.  fdf_brief_pattern writes a deterministic
+ * default: xorshift32 with state s = 0x9E3779B9, next() = { s ^= s << 13; s ^= s >> 17;
+ * s ^= s << 5; return s; } in uint32, coord() = the sum of six successive next() >> 29, minus
+ * 21 (bell-shaped in -21..21).  A draw is x0, y0, x1, y1 from four coord() calls in that
+ * order; it is rejected if either point has x^2 + y^2 > 13^2, if the two points are equal or
+ * if the same 4-tuple was accepted before; 256 tests are accepted (after 278 draws; test 0 is
+ * 5, 8, -11, -2; crc32 of the bytes 1958958545).  Host only, no context.
+ *
+ * Steering table.  fdf_brief_steer writes n_bins x 256 x 4 int8, 1 <= n_bins <= 360: bin b
+ * holds every pattern point rotated by theta = 2 pi b / n_bins with y pointing down (the
+ * angle of fdf_orient_device): x' = x cos theta - y sin theta, y' = x sin theta + y cos theta,
+ * computed in double, rounded to float, that float rounded half away from zero to an integer
+ * and saturated to int8.  Bin 0 is the pattern itself.  Host only; FDF_ERR_ARG for a NULL
+ * pointer or n_bins outside 1..360.
+ *
+ * Bin of an angle.  With scale = (float)(n_bins / (2 pi)) (computed in double), t = the float
+ * product angle * scale (rounded once, not fused), the bin is t rounded to the nearest integer,
+ * ties to even, taken modulo n_bins into [0, n_bins).  An angle for which |angle| <= 7 is false
+ * (NaN and the infinities included) has bin 0.  d_angles == NULL means bin 0 for every point:
+ * unsteered BRIEF.
+ *
+ * Descriptor.  For the keypoint (x, y) in bin b, bit i is 1 iff I(x + x0, y + y0) <
+ * I(x + x1, y + y1) with (x0, y0, x1, y1) = table[b][i] and I read at coordinates clamped to
+ * the frame (the replicated border of fdf_orient_device).  Bit i is bit i % 8 of byte i / 8
+ * (test 0 is the least significant bit of byte 0, OpenCV's packing); 32 bytes per keypoint.
+ *
+ * Smoothing.  out(x, y) = (sum over |dx| <= 2, |dy| <= 2 of I(clamp(x + dx), clamp(y + dy))
+ * + 12) / 25 in integers, for any width, height >= 1 with width * height <= 2^31 - 256
+ * (FDF_ERR_SIZE otherwise).  Frames may be any number of bytes apart on either side; the gap
+ * bytes of the output are not written; input and output must not overlap.  The descriptor
+ * step reads whatever frames it is given: smoothing is the caller's choice.
+ *
+ * fdf_smooth_device, fdf_describe_device: asynchronous on `stream` (NULL = the HIP null
+ * stream); like fdf_orient_device they take no context lock and use no context workspace, they
+ * only bind the context's device; nothing is allocated and nothing returns to the host.
+ * fdf_describe_device's indexing is fdf_orient_device's: frame f owns the indices [offs[f],
+ * min(offs[f+1], cap)), d_desc gets 32 bytes per point and entries at index >=
+ * min(offs[n_frames], cap) are not written.  FDF_ERR_ARG, synchronously and with nothing
+ * launched: a NULL required pointer, n_frames > 65535, a frame stride below width * height when
+ * n_frames > 1, n_bins outside 1..360.  For fdf_describe_device shape errors and empty shapes
+ * are as for fdf_orient_device (FDF_OK, nothing written).  A point with x >= width or
+ * y >= height gives an unspecified descriptor.  Whatever the points, angles and table hold, no
+ * access leaves the frames' bytes or the other buffers.  Frames, table and descriptors may have any alignment.
+ *
+ * fdf_describe_points: one host frame (rows stride_bytes apart, any width, height >= 1) and
+ * host points, synchronous; angles may be NULL, pattern NULL is the default pattern, smooth is
+ * 0 or 1 (1: the descriptors are taken from the smoothed frame).  Points outside the image are
+ * rejected with FDF_ERR_ARG.  Copies through device buffers allocated and freed by the call
+ * and runs the same kernels; the context's workspace and retained result are untouched, so
+ * fdf_fetch_last stays valid.
+ */
+int fdf_brief_pattern(int8_t pattern[1024]);
+int fdf_brief_steer(const int8_t* pattern, uint32_t n_bins, int8_t* table);
+int fdf_smooth_device(fdf_ctx* ctx, const uint8_t* d_frames, uint32_t n_frames, uint32_t width,
+                      uint32_t height, uint64_t frame_stride_bytes, uint8_t* d_out,
+                      uint64_t out_frame_stride_bytes, void* stream);
+int fdf_describe_device(fdf_ctx* ctx, const uint8_t* d_frames, uint32_t n_frames, uint32_t width,
+                        uint32_t height, uint64_t frame_stride_bytes, const fdf_point* d_points,
+                        uint64_t cap, const uint64_t* d_frame_offsets, const float* d_angles,
+                        const int8_t* d_table, uint32_t n_bins, uint8_t* d_desc, void* stream);
+int fdf_describe_points(fdf_ctx* ctx, const uint8_t* data, uint32_t width, uint32_t height,
+                        size_t stride_bytes, const fdf_point* points, size_t n_points,
+                        const float* angles, const int8_t* pattern, uint32_t n_bins, int smooth,
+                        uint8_t* out_desc);
 
 /*
  * Streaming host pipeline (extension; the reference's callers detect on one

@@ -16,6 +16,7 @@
 //   image::GrayImage                (image 0.24.6)       fdf::GrayView (borrowed row-major u8)
 //   (none: callers keep the best K)  --                   fdf::select_best(points, scores, ...)
 //   (none: ORB-style callers orient) --                   fdf::keypoint_angles(img, points, ...)
+//   (none: ... and describe)         --                   fdf::keypoint_descriptors(img, points, ...)
 //
 // Where the reference panics (n < 9, n > 16, degenerate sizes) these throw fdf::Error.
 // Each thread lazily owns one device context per HIP device (device 0 unless
@@ -236,6 +237,35 @@ inline std::vector<float> keypoint_angles(const GrayView& img, const std::vector
                                           uint32_t radius = 15,
                                           std::vector<int32_t>* moments = nullptr) {
     return keypoint_angles(img, points, radius, thread_context(), moments);
+}
+
+// Steered BRIEF descriptors (extension, fdf_describe_points): 32 bytes per point of one image,
+// test i in bit i % 8 of byte i / 8.  `angles` (optional, one per point, as keypoint_angles
+// returns them) pick one of `n_bins` (1..360) rotations of `pattern` (optional, 256 tests of
+// x0, y0, x1, y1; the default is fdf_brief_pattern's); with `smooth` the tests read the
+// 5 x 5 box-smoothed image.
+inline std::vector<uint8_t> keypoint_descriptors(const GrayView& img,
+                                                 const std::vector<Point>& points,
+                                                 const std::vector<float>* angles,
+                                                 const std::array<int8_t, 1024>* pattern,
+                                                 uint32_t n_bins, bool smooth, Context& ctx) {
+    if (angles && angles->size() != points.size())
+        throw Error(FDF_ERR_ARG, "keypoint_descriptors: one angle per point");
+    std::vector<uint8_t> desc(32 * points.size());
+    check(fdf_describe_points(ctx.get(), img.data, img.width, img.height, img.stride,
+                              reinterpret_cast<const fdf_point*>(points.data()), points.size(),
+                              angles ? angles->data() : nullptr,
+                              pattern ? pattern->data() : nullptr, n_bins, smooth ? 1 : 0,
+                              desc.data()),
+          "fdf_describe_points");
+    return desc;
+}
+inline std::vector<uint8_t> keypoint_descriptors(const GrayView& img,
+                                                 const std::vector<Point>& points,
+                                                 const std::vector<float>* angles = nullptr,
+                                                 const std::array<int8_t, 1024>* pattern = nullptr,
+                                                 uint32_t n_bins = 30, bool smooth = true) {
+    return keypoint_descriptors(img, points, angles, pattern, n_bins, smooth, thread_context());
 }
 
 inline std::vector<Point> detect(const GrayView& img, const Config& config) {
