@@ -2,10 +2,9 @@
 #   libfdf.so        HIP kernels + C ABI (the product), gfx950 only
 #   liboracle.so     scalar C restatement of the reference semantics (test infrastructure)
 #   libfast_avx2.so  C++ AVX2 port of the reference's fast_simd path (CPU baseline only)
-#   test_cpp_api     C++ API (include/fdf.hpp) smoke binary
-#   test_cpp_select  fdf::select_best smoke binary
-#   test_cpp_orient  fdf::keypoint_angles smoke binary
-#   test_cpp_describe  fdf::keypoint_descriptors smoke binary
+#   tests/cpp/test_cpp_*   smoke binaries of the C++ API (include/fdf.hpp): detection,
+#                          fdf::select_best, fdf::keypoint_angles, fdf::keypoint_descriptors
+#   tests/cpp/test_wg_share  host-only check of the kernels' work split (fdf_common.h)
 HIPCC ?= /opt/rocm/bin/hipcc
 CC ?= gcc
 CXX ?= g++
@@ -15,37 +14,20 @@ PKG := feature_detector_fast_amd
 CSRC := $(PKG)/csrc
 LIBFDF := $(PKG)/libfdf.so
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Iinclude $(EXTRA_HIPFLAGS)
+OBJS := $(addprefix $(CSRC)/fdf_,$(addsuffix .o,kernels sweep sweep_latency sweep_rgb select \
+	orient describe api stages pipeline))
+HEADERS := $(wildcard $(CSRC)/*.h) include/fdf.h
+CPP_TESTS := $(addprefix tests/cpp/test_cpp_,api select orient describe)
 
-all: $(LIBFDF) oracle/liboracle.so oracle/libfast_avx2.so tests/cpp/test_cpp_api tests/cpp/test_cpp_select tests/cpp/test_cpp_orient tests/cpp/test_cpp_describe
+all: $(LIBFDF) oracle/liboracle.so oracle/libfast_avx2.so $(CPP_TESTS) tests/cpp/test_wg_share
 
-$(CSRC)/fdf_kernels.o: $(CSRC)/fdf_kernels.hip $(CSRC)/fdf_compact.h $(CSRC)/fdf_kernels.h $(CSRC)/fdf_common.h
+$(CSRC)/%.o: $(CSRC)/%.hip $(HEADERS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(CSRC)/fdf_sweep.o: $(CSRC)/fdf_sweep.hip $(CSRC)/fdf_sweep_impl.h $(CSRC)/fdf_compact.h $(CSRC)/fdf_kernels.h $(CSRC)/fdf_common.h
+$(CSRC)/%.o: $(CSRC)/%.cpp $(HEADERS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(CSRC)/fdf_sweep_latency.o: $(CSRC)/fdf_sweep_latency.hip $(CSRC)/fdf_sweep_impl.h $(CSRC)/fdf_compact.h $(CSRC)/fdf_kernels.h $(CSRC)/fdf_common.h
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(CSRC)/fdf_sweep_rgb.o: $(CSRC)/fdf_sweep_rgb.hip $(CSRC)/fdf_sweep_impl.h $(CSRC)/fdf_compact.h $(CSRC)/fdf_kernels.h $(CSRC)/fdf_common.h
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(CSRC)/fdf_select.o: $(CSRC)/fdf_select.hip $(CSRC)/fdf_kernels.h $(CSRC)/fdf_common.h
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(CSRC)/fdf_orient.o: $(CSRC)/fdf_orient.hip $(CSRC)/fdf_kernels.h $(CSRC)/fdf_common.h
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(CSRC)/fdf_describe.o: $(CSRC)/fdf_describe.hip $(CSRC)/fdf_kernels.h $(CSRC)/fdf_common.h
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(CSRC)/fdf_api.o: $(CSRC)/fdf_api.cpp $(CSRC)/fdf_kernels.h include/fdf.h
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(CSRC)/fdf_pipeline.o: $(CSRC)/fdf_pipeline.cpp include/fdf.h
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIBFDF): $(CSRC)/fdf_kernels.o $(CSRC)/fdf_sweep.o $(CSRC)/fdf_sweep_latency.o $(CSRC)/fdf_sweep_rgb.o $(CSRC)/fdf_select.o $(CSRC)/fdf_orient.o $(CSRC)/fdf_describe.o $(CSRC)/fdf_api.o $(CSRC)/fdf_pipeline.o
+$(LIBFDF): $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
 
 oracle/liboracle.so: oracle/fast_oracle.c oracle/fast_oracle.h
@@ -54,17 +36,12 @@ oracle/liboracle.so: oracle/fast_oracle.c oracle/fast_oracle.h
 oracle/libfast_avx2.so: oracle/fast_avx2.cpp
 	$(CXX) -O3 -mavx2 -std=c++17 -fPIC -shared -Wall -o $@ $< -lpthread
 
-tests/cpp/test_cpp_api: tests/cpp/test_cpp_api.cpp include/fdf.hpp include/fdf.h $(LIBFDF)
+tests/cpp/%: tests/cpp/%.cpp include/fdf.hpp include/fdf.h $(LIBFDF)
 	$(CXX) -O2 -std=c++17 -Wall -Iinclude -o $@ $< -L$(PKG) -lfdf -Wl,-rpath,'$$ORIGIN/../../$(PKG)'
 
-tests/cpp/test_cpp_select: tests/cpp/test_cpp_select.cpp include/fdf.hpp include/fdf.h $(LIBFDF)
-	$(CXX) -O2 -std=c++17 -Wall -Iinclude -o $@ $< -L$(PKG) -lfdf -Wl,-rpath,'$$ORIGIN/../../$(PKG)'
-
-tests/cpp/test_cpp_orient: tests/cpp/test_cpp_orient.cpp include/fdf.hpp include/fdf.h $(LIBFDF)
-	$(CXX) -O2 -std=c++17 -Wall -Iinclude -o $@ $< -L$(PKG) -lfdf -Wl,-rpath,'$$ORIGIN/../../$(PKG)'
-
-tests/cpp/test_cpp_describe: tests/cpp/test_cpp_describe.cpp include/fdf.hpp include/fdf.h $(LIBFDF)
-	$(CXX) -O2 -std=c++17 -Wall -Iinclude -o $@ $< -L$(PKG) -lfdf -Wl,-rpath,'$$ORIGIN/../../$(PKG)'
+# fdf_common.h is a HIP header: the compiler's host pass alone, no device code, no libfdf.so
+tests/cpp/test_wg_share: tests/cpp/test_wg_share.cpp $(CSRC)/fdf_common.h $(CSRC)/fdf_kernels.h
+	$(HIPCC) -x hip --offload-host-only -O2 -std=c++17 -Wall -o $@ $<
 
 # Ablation build (tools/ablate.py, tools/pmc_ablate.sh): the same library with the internal
 # FDF_DEBUG_FLAGS / FDF_NSUB / FDF_LDS_BUDGET / FDF_COMPACT_TPG switches compiled in.
@@ -74,7 +51,6 @@ build/libfdf_debug.so: $(CSRC)/*.hip $(CSRC)/*.cpp $(CSRC)/*.h include/fdf.h
 	bash tools/build_variant.sh debug "-DFDF_DEBUG_BUILD"
 
 clean:
-	rm -f $(CSRC)/*.o $(LIBFDF) oracle/*.so tests/cpp/test_cpp_api tests/cpp/test_cpp_select \
-		tests/cpp/test_cpp_orient tests/cpp/test_cpp_describe
+	rm -f $(CSRC)/*.o $(LIBFDF) oracle/*.so $(CPP_TESTS) tests/cpp/test_wg_share
 
 .PHONY: all clean debug

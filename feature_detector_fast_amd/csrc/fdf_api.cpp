@@ -1,4 +1,5 @@
-// fdf_api.cpp -- the C ABI of include/fdf.h on top of the HIP kernels.
+// fdf_api.cpp -- the C ABI of include/fdf.h on top of the HIP kernels: contexts, detection,
+// scoring, fetch, rings and multi-device calls (the stages behind the detector: fdf_stages.cpp).
 //
 // Replaces fast_simd::detector (iwanders/feature_detector_fast src/fast_simd.rs:847-859):
 // validation mirrors the reference's panics (:302-305, :342, :369, :800) as status codes,
@@ -8,7 +9,6 @@
 
 #include <algorithm>
 #include <atomic>
-#include <cmath>
 #include <cstdint>
 #include <cstdlib>
 #include <cstdio>
@@ -20,116 +20,7 @@
 #include <new>
 
 #include "../../include/fdf.h"
-#include "fdf_kernels.h"
-
-// Result of the last host-API detection on a context (fdf_fetch_last): its points stay in
-// d_out, its offsets in d_offsets and its frames in d_in until the next host call.
-struct LastResult {
-    bool valid = false;
-    bool host_out = false;         // the points / offsets are in the host-mapped h_out / h_offs
-    uint64_t total = 0;
-    uint32_t n_frames = 0, width = 0, height = 0;
-    fdf_config cfg{};
-    bool rgb = false;              // frames in d_rgb (RGB8); scores need their luma in d_in
-    bool in_place = false;         // the frame was read in place from pinned host memory: not
-                                   // in d_in, so the result has no scores (fdf_fetch_last)
-    // fdf_detect_batch_multi: the call's generation (0: not a multi-context result) and this
-    // context's shard of it, checked by fdf_fetch_last_multi
-    uint64_t multi_gen = 0;
-    uint32_t shard = 0, nshards = 0;
-};
-
-struct fdf_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::mutex mu;
-    // device workspace, grown on demand
-    uint8_t* d_in = nullptr;            size_t in_bytes = 0;       // host-API frame staging
-    uint8_t* d_rgb = nullptr;           size_t rgb_bytes = 0;      // host-API RGB staging
-    uint2* d_out = nullptr;             size_t out_points = 0;     // host-API output
-    uint64_t* d_offsets = nullptr;      size_t offsets_n = 0;      // host-API frame offsets
-    // host-API output in pinned, device-mapped host memory: the detector (direct output) or
-    // the compaction writes the points and offsets there over PCIe, so a host call needs no
-    // copy kernel, no device-to-host copy and one synchronisation (hd_*: device addresses)
-    uint2* h_out = nullptr;             uint2* hd_out = nullptr;   size_t h_out_points = 0;
-    uint64_t* h_offs = nullptr;         uint64_t* hd_offs = nullptr;   size_t h_offs_n = 0;
-    // fdf_detect's overlapped upload: the frame goes up in row chunks on copy_stream, each
-    // chunk's flag (pinned, device-mapped) set to the call's epoch after its copy, while the
-    // detector already runs and each band waits for the chunk of its last row
-    hipStream_t copy_stream = nullptr;
-    uint32_t* h_flags = nullptr;        // pinned: the epoch each chunk's flag copy carries
-    uint32_t* d_flags = nullptr;        // device: the chunk flags the bands poll
-    uint32_t chunk_epoch = 0;
-    uint32_t chunks = 0;                // upload chunks (0: kChunksDefault; 1: no overlap)
-    // host frames that start in pinned memory but run past its mapping (a hipHostRegister'ed
-    // range shorter than the frames) are packed into this pinned buffer by the CPU first: the
-    // runtime's DMA copy rejects such a source range
-    uint8_t* h_stage = nullptr;         uint8_t* hd_stage = nullptr;   size_t h_stage_bytes = 0;
-    // recoveries the host entry points made on their own (fdf_ctx_recoveries): a band's wait
-    // for its upload chunk ran out and the frame was detected again from one copy; a
-    // direct-output look-back ran out and the compaction rebuilt the output from the slots
-    uint64_t upload_fallbacks = 0, lookback_recoveries = 0;
-    // an asynchronous device call's look-back ran out and a host call found the error word
-    // first: kept here and returned by the next fdf_detect_device(_rgb), as fdf.h promises
-    bool pending_device_error = false;
-    uint16_t* d_scores = nullptr;       size_t scores_n = 0;       // host-API scores
-    uint8_t* d_slots = nullptr;         size_t slots_bytes = 0;    // per-band output slots
-    uint32_t* d_counts = nullptr;       size_t counts_n = 0;       // per-band keypoint counts
-    // compaction bases: two alternating buffers of per-group sums (kept zero between uses)
-    // and the keypoint-statistics word, all zeroed once at context creation
-    uint32_t* d_sums = nullptr;         // 2 x fdfk::kMaxGroupSums, then 4 words
-    int sums_parity = 0;
-    bool sums_dirty = false;            // a launch failed: re-zero before the next use
-    // NMS keypoint density feedback (band height): the compaction writes the last finished
-    // launch's pre-NMS keypoint total to host-mapped memory, tagged with its launch number
-    uint64_t* h_stats = nullptr;        // pinned, mapped; *h_stats = seq << 32 | total;
-                                        // h_stats[1]: the direct output's look-back error word
-    uint64_t* d_stats = nullptr;        // its device address
-    uint32_t stats_seq = 0;
-    struct LaunchInfo { uint32_t seq = 0, t = 0, n = 0, nms = 0, w = 0; double pixels = 0; };
-    LaunchInfo hist[64];
-    // the last density read, kept for its configuration: with more launches in flight than
-    // `hist` holds, a read finds its launch's record overwritten (the band height then
-    // alternated between launches of one configuration)
-    // (one per NMS mode, so that interleaved modes keep theirs)
-    LaunchInfo known[3];
-    double known_density[3] = {0.0, 0.0, 0.0};
-    // cross-stream ordering: the device work of the last enqueue (on any stream) completes
-    // at `done`; the next enqueue on another stream waits for it first
-    hipEvent_t done = nullptr;
-    hipStream_t done_stream = nullptr;
-    bool done_valid = false;
-    // the last enqueue's work is on done_stream but `done` is not recorded after it yet: on
-    // the context's own stream and the null stream (streams that outlive every call) the
-    // record waits until something needs it (another stream's call, a host wait), so a
-    // stream of back-to-back calls enqueues one packet per call, not two
-    bool done_pending = false;
-    // the last enqueue's compaction, relaunched when the host output has to grow
-    fdfk::CompactParams last_compact{};
-    LastResult last;
-    // grid size that counts as filling the chip (fdf_ctx_set_geometry; 0 = kDefaultMinTasks)
-    uint64_t min_tasks = 0;
-    uint32_t band_rows = 0;              // fdf_ctx_set_band_rows (0 = automatic)
-    // optional per-kernel timing (fdf_ctx_set_timing): every `timing`-th call (0: off) records
-    // its kernels' durations
-    uint32_t timing = 0;
-    uint64_t timing_calls = 0;            // calls since timing was enabled
-    size_t timed = 0;                     // calls recorded since timing was enabled
-    std::vector<hipEvent_t> ev;           // 4 per recorded call, kMaxTimedCalls at most
-    std::vector<uint8_t> timed_compact;   // per recorded call: 1 if it launched the compaction
-    // direct output of small grids (BandParams::direct): look-back descriptors, launch tag
-    uint64_t* d_lookback = nullptr;       size_t lookback_n = 0;
-    // band tickets: the device counter (a spare word of d_sums, zeroed with it) has handed out
-    // ticket_next tickets, ntasks per direct launch
-    uint32_t ticket_next = 0;
-    uint32_t cus = 0;                     // compute units of the device
-    // workgroups per CU of a detector instance (sweep_occupancy), by configuration
-    struct Occupancy { uint32_t nms, n, lds; bool rgb; uint32_t wg; };
-    std::vector<Occupancy> occupancy;
-    // debug builds (FDF_STAMPS set): the last detector launch's workgroup stamps
-    uint64_t* d_stamps = nullptr;         size_t stamps_n = 0;
-    uint64_t stamps_used = 0;             // words written by the last launch
-};
+#include "fdf_ctx.h"
 
 constexpr size_t kMaxTimedCalls = 4096;
 constexpr uint64_t kDefaultMinTasks = 1024;   // 4 workgroups on each of 256 CUs
@@ -146,34 +37,6 @@ std::atomic<uint64_t> g_multi_gen{0};
 std::atomic<uint32_t> g_launch_epoch{0};
 
 namespace {
-
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-int check_config(const fdf_config* cfg) {
-    if (!cfg) return FDF_ERR_ARG;
-    if (cfg->count < 9 || cfg->count > 16) return FDF_ERR_COUNT;
-    if (cfg->nms > FDF_NMS_SUM_ABSOLUTE) return FDF_ERR_NMS;
-    return FDF_OK;
-}
-
-// Shape rules derived from the reference's u32 arithmetic (SURVEY.md §7 "Errors").
-int check_shape(uint32_t w, uint32_t h, int* empty) {
-    *empty = 0;
-    if (h < 3) return FDF_ERR_SIZE;        // height - 3 underflows (src/fast_simd.rs:342)
-    if (h <= 6) { *empty = 1; return FDF_OK; }
-    if (w < 6) return FDF_ERR_SIZE;        // width - 3 - 3 underflows (:369)
-    if (w == 6) { *empty = 1; return FDF_OK; }
-    return FDF_OK;
-}
 
 // `done` covers the last enqueue's work (recorded now if that was deferred).
 hipError_t record_done(fdf_ctx* ctx) {
@@ -1441,532 +1304,6 @@ int fdf_score_points(fdf_ctx* ctx, const uint8_t* data, uint32_t width, uint32_t
         e = hipMemcpyAsync(out_scores, d_scores, n_points * sizeof(uint16_t), hipMemcpyDeviceToHost,
                            ctx->stream);
     if (e == hipSuccess) e = sync_own_stream(ctx);
-    return e == hipSuccess ? FDF_OK : FDF_ERR_DEVICE;
-}
-
-// ---- best-K selection per grid cell (fdf_select.hip) -------------------------------------
-namespace {
-
-// Scratch of one fdf_select_device call, every part 256-byte aligned: the per-frame kept
-// totals (zeroed on the stream before the kernels), the kept count and the index range of
-// every (frame, cell row), and `cap` keep flags for a caller that passes no d_keep.
-struct SelectLayout {
-    uint32_t cw = 0, ch = 0, cells_x = 0, rows = 0;
-    uint64_t frame_tot = 0, row_cnt = 0, row_range = 0, keep = 0, total = 0;
-};
-
-inline uint64_t align256(uint64_t v) { return (v + 255u) & ~255ull; }
-
-// FDF_OK with *empty set for shapes with no keypoints; the shape's error otherwise.
-int select_layout(uint32_t n_frames, uint32_t width, uint32_t height, uint32_t cell_w,
-                  uint32_t cell_h, uint64_t cap, SelectLayout* L, int* empty) {
-    int rc = check_shape(width, height, empty);
-    if (rc) return rc;
-    if (n_frames > 65535u || (uint64_t)width * height > 0xffffffffull) return FDF_ERR_ARG;
-    if (n_frames == 0) *empty = 1;
-    if (*empty) return FDF_OK;
-    L->cw = cell_w == 0 || cell_w > width ? width : cell_w;
-    L->ch = cell_h == 0 || cell_h > height ? height : cell_h;
-    L->cells_x = (width + L->cw - 1) / L->cw;
-    L->rows = (height + L->ch - 1) / L->ch;
-    if (L->rows > fdfk::kSelMaxRows) return FDF_ERR_ARG;
-    const uint64_t nrows = (uint64_t)n_frames * L->rows;
-    L->frame_tot = 0;
-    L->row_cnt = align256(sizeof(uint64_t) * n_frames);
-    L->row_range = L->row_cnt + align256(sizeof(uint32_t) * nrows);
-    L->keep = L->row_range + align256(2 * sizeof(uint64_t) * nrows);
-    if (cap > ~0ull - L->keep - 256u) return FDF_ERR_ARG;
-    L->total = L->keep + align256(cap);
-    return FDF_OK;
-}
-
-}  // namespace
-
-int fdf_select_scratch_bytes(uint32_t n_frames, uint32_t width, uint32_t height,
-                             uint32_t cell_w, uint32_t cell_h, uint64_t cap, uint64_t* bytes) {
-    if (!bytes) return FDF_ERR_ARG;
-    SelectLayout L;
-    int empty = 0;
-    const int rc = select_layout(n_frames, width, height, cell_w, cell_h, cap, &L, &empty);
-    if (rc) return rc;
-    *bytes = empty ? 0 : L.total;
-    return FDF_OK;
-}
-
-int fdf_select_device(fdf_ctx* ctx, uint32_t n_frames, uint32_t width, uint32_t height,
-                      const fdf_point* d_points, const uint16_t* d_scores, uint64_t cap,
-                      const uint64_t* d_frame_offsets, uint32_t cell_w, uint32_t cell_h,
-                      uint32_t k, fdf_point* d_sel, uint16_t* d_sel_scores, uint64_t sel_cap,
-                      uint64_t* d_sel_offsets, uint8_t* d_keep, void* d_scratch,
-                      uint64_t scratch_bytes, void* stream) {
-    if (!ctx || !d_sel_offsets || k == 0) return FDF_ERR_ARG;
-    SelectLayout L;
-    int empty = 0;
-    const int rc = select_layout(n_frames, width, height, cell_w, cell_h, cap, &L, &empty);
-    if (rc) return rc;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);   // NULL = the HIP null stream
-    if (!empty) {
-        if (!d_frame_offsets || !d_scratch || scratch_bytes < L.total ||
-            ((uintptr_t)d_scratch & 255u) != 0)
-            return FDF_ERR_ARG;
-        if (cap && (!d_points || !d_scores)) return FDF_ERR_ARG;
-        if (sel_cap && (!d_sel || !d_sel_scores)) return FDF_ERR_ARG;
-    }
-    DeviceGuard guard(ctx->device);
-    if (empty || cap == 0) {
-        return hipMemsetAsync(d_sel_offsets, 0, sizeof(uint64_t) * (n_frames + 1ull), s) ==
-                       hipSuccess
-                   ? FDF_OK
-                   : FDF_ERR_DEVICE;
-    }
-    uint8_t* base = static_cast<uint8_t*>(d_scratch);
-    fdfk::SelectParams p{};
-    p.pts = reinterpret_cast<const uint2*>(d_points);
-    p.scores = d_scores;
-    p.offs = d_frame_offsets;
-    p.cap = cap;
-    p.n_frames = n_frames;
-    p.cw = L.cw;
-    p.ch = L.ch;
-    p.cells_x = L.cells_x;
-    p.rows = L.rows;
-    p.k = k;
-    p.keep = d_keep ? d_keep : base + L.keep;
-    p.frame_tot = reinterpret_cast<uint64_t*>(base + L.frame_tot);
-    p.row_cnt = reinterpret_cast<uint32_t*>(base + L.row_cnt);
-    p.row_range = reinterpret_cast<uint64_t*>(base + L.row_range);
-    p.sel = reinterpret_cast<uint2*>(d_sel);
-    p.sel_scores = d_sel_scores;
-    p.sel_cap = sel_cap;
-    p.sel_offs = d_sel_offsets;
-    // the frame totals are summed into; the keep flags of indices no frame owns stay 0
-    hipError_t e = hipMemsetAsync(p.frame_tot, 0, sizeof(uint64_t) * n_frames, s);
-    if (e == hipSuccess) e = hipMemsetAsync(p.keep, 0, cap, s);
-    if (e == hipSuccess) e = fdfk::launch_select(p, s);
-    return e == hipSuccess ? FDF_OK : FDF_ERR_DEVICE;
-}
-
-int fdf_select_points(fdf_ctx* ctx, const fdf_point* points, const uint16_t* scores,
-                      const uint64_t* frame_offsets, uint32_t n_frames, size_t n_points,
-                      uint32_t width, uint32_t height, uint32_t cell_w, uint32_t cell_h,
-                      uint32_t k, fdf_point* out, uint16_t* out_scores, size_t cap,
-                      uint64_t* out_offsets, size_t* n_out) {
-    if (!ctx || !n_out || k == 0) return FDF_ERR_ARG;
-    if (n_points && (!points || !scores)) return FDF_ERR_ARG;
-    if (cap && (!out || !out_scores)) return FDF_ERR_ARG;
-    if (!frame_offsets && n_frames != 1) return FDF_ERR_ARG;
-    SelectLayout L;
-    int empty = 0;
-    const int rc = select_layout(n_frames, width, height, cell_w, cell_h, n_points, &L, &empty);
-    if (rc) return rc;
-    *n_out = 0;
-    if (empty || n_points == 0) {
-        if (out_offsets) std::memset(out_offsets, 0, sizeof(uint64_t) * (n_frames + 1ull));
-        return FDF_OK;
-    }
-    // one allocation for the call, cut into 256-byte aligned parts; the context's workspace
-    // and retained result (fdf_fetch_last) are not touched
-    const uint64_t noffs = n_frames + 1ull;
-    const uint64_t o_pts = 0;
-    const uint64_t o_scores = o_pts + align256(n_points * sizeof(fdf_point));
-    const uint64_t o_offs = o_scores + align256(n_points * sizeof(uint16_t));
-    const uint64_t o_sel = o_offs + align256(noffs * sizeof(uint64_t));
-    const uint64_t o_sel_scores = o_sel + align256((uint64_t)cap * sizeof(fdf_point));
-    const uint64_t o_sel_offs = o_sel_scores + align256((uint64_t)cap * sizeof(uint16_t));
-    const uint64_t o_scratch = o_sel_offs + align256(noffs * sizeof(uint64_t));
-    const uint64_t bytes = o_scratch + L.total;
-    std::lock_guard<std::mutex> lock(ctx->mu);    // the context's stream carries the call
-    DeviceGuard guard(ctx->device);
-    uint8_t* d = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&d), bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return FDF_ERR_ALLOC;
-    }
-    const uint64_t one_frame[2] = {0, n_points};
-    std::vector<uint64_t> offs(noffs);
-    hipStream_t s = ctx->stream;
-    hipError_t e = hipMemcpyAsync(d + o_pts, points, n_points * sizeof(fdf_point),
-                                  hipMemcpyHostToDevice, s);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(d + o_scores, scores, n_points * sizeof(uint16_t),
-                           hipMemcpyHostToDevice, s);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(d + o_offs, frame_offsets ? frame_offsets : one_frame,
-                           noffs * sizeof(uint64_t), hipMemcpyHostToDevice, s);
-    int status = FDF_OK;
-    if (e == hipSuccess)
-        status = fdf_select_device(ctx, n_frames, width, height,
-                                   reinterpret_cast<const fdf_point*>(d + o_pts),
-                                   reinterpret_cast<const uint16_t*>(d + o_scores), n_points,
-                                   reinterpret_cast<const uint64_t*>(d + o_offs), cell_w, cell_h,
-                                   k, reinterpret_cast<fdf_point*>(d + o_sel),
-                                   reinterpret_cast<uint16_t*>(d + o_sel_scores), cap,
-                                   reinterpret_cast<uint64_t*>(d + o_sel_offs), nullptr,
-                                   d + o_scratch, L.total, s);
-    if (e == hipSuccess && status == FDF_OK)
-        e = hipMemcpyAsync(offs.data(), d + o_sel_offs, noffs * sizeof(uint64_t),
-                           hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && status == FDF_OK) e = hipStreamSynchronize(s);
-    if (e == hipSuccess && status == FDF_OK) {
-        const uint64_t total = offs[n_frames];
-        const uint64_t ncopy = std::min<uint64_t>(total, cap);
-        if (ncopy) {
-            e = hipMemcpyAsync(out, d + o_sel, ncopy * sizeof(fdf_point), hipMemcpyDeviceToHost, s);
-            if (e == hipSuccess)
-                e = hipMemcpyAsync(out_scores, d + o_sel_scores, ncopy * sizeof(uint16_t),
-                                   hipMemcpyDeviceToHost, s);
-            if (e == hipSuccess) e = hipStreamSynchronize(s);
-        }
-        if (e == hipSuccess) {
-            *n_out = (size_t)total;
-            if (out_offsets) std::memcpy(out_offsets, offs.data(), noffs * sizeof(uint64_t));
-            if (total > cap) status = FDF_ERR_CAPACITY;
-        }
-    }
-    if (e != hipSuccess) (void)hipStreamSynchronize(s);    // nothing may still use `d`
-    (void)hipFree(d);
-    if (e != hipSuccess) return FDF_ERR_DEVICE;
-    return status;
-}
-
-// ---- orientation by intensity centroid (fdf_orient.hip) ---------------------------------
-
-int fdf_orient_disc(uint32_t radius, uint8_t* half_widths) {
-    if (radius == 0 || radius > fdfk::kOrientMaxRadius || !half_widths) return FDF_ERR_ARG;
-    // OpenCV's umax: the rounded circle for the rows up to r / sqrt(2), mirrored for the rest
-    // so that the disc is symmetric about its diagonal
-    const int r = (int)radius;
-    const int vmax = (int)std::floor(r * std::sqrt(2.0) / 2 + 1);
-    const int vmin = (int)std::ceil(r * std::sqrt(2.0) / 2);
-    int u[fdfk::kOrientMaxRadius + 2] = {0};
-    for (int v = 0; v <= vmax; ++v)
-        u[v] = (int)std::floor(std::sqrt((double)r * r - (double)v * v) + 0.5);
-    for (int v = r, v0 = 0; v >= vmin; --v) {
-        while (u[v0] == u[v0 + 1]) ++v0;
-        u[v] = v0;
-        ++v0;
-    }
-    for (int v = 0; v <= r; ++v) half_widths[v] = (uint8_t)u[v];
-    return FDF_OK;
-}
-
-namespace {
-
-// The launch of fdf_orient_device / fdf_orient_points (arguments already validated).
-hipError_t orient_enqueue(const uint8_t* d_frames, uint32_t n_frames, uint32_t width,
-                          uint32_t height, uint64_t frame_stride, const fdf_point* d_points,
-                          uint64_t cap, const uint64_t* d_offsets, uint32_t radius,
-                          float* d_angles, int32_t* d_moments, hipStream_t s) {
-    fdfk::OrientParams p{};
-    p.frames = d_frames;
-    p.frame_stride = frame_stride;
-    p.pts = reinterpret_cast<const uint2*>(d_points);
-    p.offs = d_offsets;
-    p.cap = cap;
-    p.n_frames = n_frames;
-    p.width = width;
-    p.height = height;
-    p.radius = radius;
-    p.angles = d_angles;
-    p.moments = d_moments;
-    if (fdf_orient_disc(radius, p.u) != FDF_OK) return hipErrorInvalidValue;
-    // workgroups per frame: about 256 points each at the detector's usual density
-    const uint64_t est = std::min<uint64_t>(cap, (uint64_t)width * height / 32 * n_frames);
-    const uint32_t chunks = (uint32_t)std::min<uint64_t>(256, est / n_frames / 256 + 1);
-    return fdfk::launch_orient(p, chunks, s);
-}
-
-}  // namespace
-
-int fdf_orient_device(fdf_ctx* ctx, const uint8_t* d_frames, uint32_t n_frames, uint32_t width,
-                      uint32_t height, uint64_t frame_stride_bytes, const fdf_point* d_points,
-                      uint64_t cap, const uint64_t* d_frame_offsets, uint32_t radius,
-                      float* d_angles, int32_t* d_moments, void* stream) {
-    if (!ctx || !d_frame_offsets || radius == 0 || radius > fdfk::kOrientMaxRadius ||
-        n_frames > 65535u)
-        return FDF_ERR_ARG;
-    int empty = 0;
-    const int rc = check_shape(width, height, &empty);
-    if (rc) return rc;
-    if (empty || n_frames == 0 || cap == 0) return FDF_OK;
-    if (!d_frames || !d_points || !d_angles) return FDF_ERR_ARG;
-    if ((uint64_t)width * height > fdfk::kOrientMaxPixels) return FDF_ERR_SIZE;
-    if (n_frames > 1 && frame_stride_bytes < (uint64_t)width * height) return FDF_ERR_ARG;
-    DeviceGuard guard(ctx->device);
-    const uint64_t fs = n_frames > 1 ? frame_stride_bytes : (uint64_t)width * height;
-    return orient_enqueue(d_frames, n_frames, width, height, fs, d_points, cap, d_frame_offsets,
-                          radius, d_angles, d_moments,
-                          reinterpret_cast<hipStream_t>(stream)) == hipSuccess
-               ? FDF_OK
-               : FDF_ERR_DEVICE;
-}
-
-int fdf_orient_points(fdf_ctx* ctx, const uint8_t* data, uint32_t width, uint32_t height,
-                      size_t stride_bytes, const fdf_point* points, size_t n_points,
-                      uint32_t radius, float* out_angles, int32_t* out_moments) {
-    if (!ctx || radius == 0 || radius > fdfk::kOrientMaxRadius) return FDF_ERR_ARG;
-    if (n_points && (!points || !out_angles || !data)) return FDF_ERR_ARG;
-    if (stride_bytes < width) return FDF_ERR_ARG;
-    for (size_t k = 0; k < n_points; ++k)
-        if (points[k].x >= width || points[k].y >= height) return FDF_ERR_ARG;
-    if (n_points == 0) return FDF_OK;
-    const uint64_t frame_bytes = (uint64_t)width * height;
-    if (frame_bytes > fdfk::kOrientMaxPixels) return FDF_ERR_SIZE;
-    // one allocation for the call, cut into 256-byte aligned parts; the context's workspace
-    // and retained result (fdf_fetch_last) are not touched
-    const uint64_t o_pts = align256(frame_bytes);
-    const uint64_t o_offs = o_pts + align256(n_points * sizeof(fdf_point));
-    const uint64_t o_ang = o_offs + 256;
-    const uint64_t o_mom = o_ang + align256(n_points * sizeof(float));
-    const uint64_t bytes = o_mom + (out_moments ? align256(n_points * 2 * sizeof(int32_t)) : 0);
-    std::lock_guard<std::mutex> lock(ctx->mu);    // the context's stream carries the call
-    DeviceGuard guard(ctx->device);
-    uint8_t* d = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&d), bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return FDF_ERR_ALLOC;
-    }
-    const uint64_t one_frame[2] = {0, n_points};
-    hipStream_t s = ctx->stream;
-    hipError_t e = stride_bytes == width
-                       ? hipMemcpyAsync(d, data, frame_bytes, hipMemcpyHostToDevice, s)
-                       : hipMemcpy2DAsync(d, width, data, stride_bytes, width, height,
-                                          hipMemcpyHostToDevice, s);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(d + o_pts, points, n_points * sizeof(fdf_point), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(d + o_offs, one_frame, sizeof(one_frame), hipMemcpyHostToDevice, s);
-    int32_t* d_mom = out_moments ? reinterpret_cast<int32_t*>(d + o_mom) : nullptr;
-    if (e == hipSuccess)
-        e = orient_enqueue(d, 1, width, height, frame_bytes,
-                           reinterpret_cast<const fdf_point*>(d + o_pts), n_points,
-                           reinterpret_cast<const uint64_t*>(d + o_offs), radius,
-                           reinterpret_cast<float*>(d + o_ang), d_mom, s);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(out_angles, d + o_ang, n_points * sizeof(float), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && out_moments)
-        e = hipMemcpyAsync(out_moments, d_mom, n_points * 2 * sizeof(int32_t),
-                           hipMemcpyDeviceToHost, s);
-    const hipError_t se = hipStreamSynchronize(s);     // nothing may still use `d`
-    if (e == hipSuccess) e = se;
-    (void)hipFree(d);
-    return e == hipSuccess ? FDF_OK : FDF_ERR_DEVICE;
-}
-
-// ---- steered BRIEF descriptors and box smoothing (fdf_describe.hip) -----------------------
-
-int fdf_brief_pattern(int8_t pattern[1024]) {
-    if (!pattern) return FDF_ERR_ARG;
-    uint32_t s = 0x9E3779B9u;
-    auto next = [&s]() {
-        s ^= s << 13;
-        s ^= s >> 17;
-        s ^= s << 5;
-        return s;
-    };
-    auto coord = [&next]() {              // bell-shaped in -21..21
-        int v = -21;
-        for (int k = 0; k < 6; ++k) v += (int)(next() >> 29);
-        return v;
-    };
-    uint32_t n = 0;
-    while (n < fdfk::kBriefTests) {
-        int t[4];
-        for (int& v : t) v = coord();
-        if (t[0] * t[0] + t[1] * t[1] > 13 * 13 || t[2] * t[2] + t[3] * t[3] > 13 * 13) continue;
-        if (t[0] == t[2] && t[1] == t[3]) continue;
-        bool seen = false;
-        for (uint32_t k = 0; k < n && !seen; ++k)
-            seen = pattern[4 * k] == t[0] && pattern[4 * k + 1] == t[1] &&
-                   pattern[4 * k + 2] == t[2] && pattern[4 * k + 3] == t[3];
-        if (seen) continue;
-        for (int k = 0; k < 4; ++k) pattern[4 * n + k] = (int8_t)t[k];
-        ++n;
-    }
-    return FDF_OK;
-}
-
-int fdf_brief_steer(const int8_t* pattern, uint32_t n_bins, int8_t* table) {
-#pragma clang fp contract(off)
-    if (!pattern || !table || n_bins == 0 || n_bins > fdfk::kBriefMaxBins) return FDF_ERR_ARG;
-    // double products and sums, one rounding to float, then half away from zero
-    auto quantise = [](double v) {
-        const float r = std::round((float)v);
-        return (int8_t)std::min(std::max(r, -128.0f), 127.0f);
-    };
-    for (uint32_t b = 0; b < n_bins; ++b) {
-        const double theta = 2 * M_PI * b / n_bins;
-        const double c = std::cos(theta), s = std::sin(theta);
-        int8_t* row = table + (size_t)b * fdfk::kBriefTableBytes;
-        for (uint32_t k = 0; k < 2 * fdfk::kBriefTests; ++k) {    // points (x, y), y pointing down
-            const double x = pattern[2 * k], y = pattern[2 * k + 1];
-            const double xc = x * c, ys = y * s, xs = x * s, yc = y * c;
-            row[2 * k] = quantise(xc - ys);
-            row[2 * k + 1] = quantise(xs + yc);
-        }
-    }
-    return FDF_OK;
-}
-
-namespace {
-
-hipError_t smooth_enqueue(const uint8_t* d_frames, uint32_t n_frames, uint32_t width,
-                          uint32_t height, uint64_t frame_stride, uint8_t* d_out,
-                          uint64_t out_stride, hipStream_t s) {
-    fdfk::SmoothParams p{};
-    p.frames = d_frames;
-    p.frame_stride = frame_stride;
-    p.out = d_out;
-    p.out_stride = out_stride;
-    p.n_frames = n_frames;
-    p.width = width;
-    p.height = height;
-    p.groups = (width + 3) / 4;
-    // the tallest strips (4 halo rows read per strip) that still leave 16 waves per CU
-    p.strip_rows = fdfk::kSmoothStripRows;
-    while (p.strip_rows > 8 &&
-           (uint64_t)p.groups * ((height + p.strip_rows - 1) / p.strip_rows) * n_frames < 256 * 1024)
-        p.strip_rows /= 2;
-    p.strips = (height + p.strip_rows - 1) / p.strip_rows;
-    return fdfk::launch_smooth(p, s);
-}
-
-// The launch of fdf_describe_device / fdf_describe_points (arguments already validated).
-hipError_t describe_enqueue(const uint8_t* d_frames, uint32_t n_frames, uint32_t width,
-                            uint32_t height, uint64_t frame_stride, const fdf_point* d_points,
-                            uint64_t cap, const uint64_t* d_offsets, const float* d_angles,
-                            const int8_t* d_table, uint32_t n_bins, uint8_t* d_desc,
-                            hipStream_t s) {
-    fdfk::DescribeParams p{};
-    p.frames = d_frames;
-    p.frame_stride = frame_stride;
-    p.pts = reinterpret_cast<const uint2*>(d_points);
-    p.offs = d_offsets;
-    p.cap = cap;
-    p.n_frames = n_frames;
-    p.width = width;
-    p.height = height;
-    p.angles = d_angles;
-    p.table = d_table;
-    p.n_bins = n_bins;
-    p.scale = (float)(n_bins / (2 * M_PI));
-    p.desc = d_desc;
-    // workgroups per frame: about 64 points each at the detector's usual density
-    const uint64_t est = std::min<uint64_t>(cap, (uint64_t)width * height / 32 * n_frames);
-    const uint32_t chunks = (uint32_t)std::min<uint64_t>(1024, est / n_frames / 64 + 1);
-    return fdfk::launch_describe(p, chunks, s);
-}
-
-}  // namespace
-
-int fdf_smooth_device(fdf_ctx* ctx, const uint8_t* d_frames, uint32_t n_frames, uint32_t width,
-                      uint32_t height, uint64_t frame_stride_bytes, uint8_t* d_out,
-                      uint64_t out_frame_stride_bytes, void* stream) {
-    if (!ctx || n_frames > 65535u) return FDF_ERR_ARG;
-    if (width == 0 || height == 0 || (uint64_t)width * height > fdfk::kOrientMaxPixels)
-        return FDF_ERR_SIZE;
-    if (n_frames == 0) return FDF_OK;
-    if (!d_frames || !d_out) return FDF_ERR_ARG;
-    const uint64_t frame_bytes = (uint64_t)width * height;
-    if (n_frames > 1 && (frame_stride_bytes < frame_bytes || out_frame_stride_bytes < frame_bytes))
-        return FDF_ERR_ARG;
-    DeviceGuard guard(ctx->device);
-    return smooth_enqueue(d_frames, n_frames, width, height,
-                          n_frames > 1 ? frame_stride_bytes : frame_bytes, d_out,
-                          n_frames > 1 ? out_frame_stride_bytes : frame_bytes,
-                          reinterpret_cast<hipStream_t>(stream)) == hipSuccess
-               ? FDF_OK
-               : FDF_ERR_DEVICE;
-}
-
-int fdf_describe_device(fdf_ctx* ctx, const uint8_t* d_frames, uint32_t n_frames, uint32_t width,
-                        uint32_t height, uint64_t frame_stride_bytes, const fdf_point* d_points,
-                        uint64_t cap, const uint64_t* d_frame_offsets, const float* d_angles,
-                        const int8_t* d_table, uint32_t n_bins, uint8_t* d_desc, void* stream) {
-    if (!ctx || !d_frame_offsets || !d_table || n_bins == 0 || n_bins > fdfk::kBriefMaxBins ||
-        n_frames > 65535u)
-        return FDF_ERR_ARG;
-    int empty = 0;
-    const int rc = check_shape(width, height, &empty);
-    if (rc) return rc;
-    if (empty || n_frames == 0 || cap == 0) return FDF_OK;
-    if (!d_frames || !d_points || !d_desc) return FDF_ERR_ARG;
-    if ((uint64_t)width * height > fdfk::kOrientMaxPixels) return FDF_ERR_SIZE;
-    if (n_frames > 1 && frame_stride_bytes < (uint64_t)width * height) return FDF_ERR_ARG;
-    DeviceGuard guard(ctx->device);
-    const uint64_t fs = n_frames > 1 ? frame_stride_bytes : (uint64_t)width * height;
-    return describe_enqueue(d_frames, n_frames, width, height, fs, d_points, cap, d_frame_offsets,
-                            d_angles, d_table, n_bins, d_desc,
-                            reinterpret_cast<hipStream_t>(stream)) == hipSuccess
-               ? FDF_OK
-               : FDF_ERR_DEVICE;
-}
-
-int fdf_describe_points(fdf_ctx* ctx, const uint8_t* data, uint32_t width, uint32_t height,
-                        size_t stride_bytes, const fdf_point* points, size_t n_points,
-                        const float* angles, const int8_t* pattern, uint32_t n_bins, int smooth,
-                        uint8_t* out_desc) {
-    if (!ctx || n_bins == 0 || n_bins > fdfk::kBriefMaxBins || (smooth != 0 && smooth != 1))
-        return FDF_ERR_ARG;
-    if (n_points && (!points || !out_desc || !data)) return FDF_ERR_ARG;
-    if (stride_bytes < width) return FDF_ERR_ARG;
-    for (size_t k = 0; k < n_points; ++k)
-        if (points[k].x >= width || points[k].y >= height) return FDF_ERR_ARG;
-    if (n_points == 0) return FDF_OK;
-    const uint64_t frame_bytes = (uint64_t)width * height;
-    if (frame_bytes > fdfk::kOrientMaxPixels) return FDF_ERR_SIZE;
-    int8_t default_pattern[fdfk::kBriefTableBytes];
-    if (!pattern) {
-        fdf_brief_pattern(default_pattern);
-        pattern = default_pattern;
-    }
-    const uint64_t table_bytes = (uint64_t)n_bins * fdfk::kBriefTableBytes;
-    std::vector<int8_t> table(table_bytes);
-    if (fdf_brief_steer(pattern, n_bins, table.data()) != FDF_OK) return FDF_ERR_ARG;
-    // one allocation for the call, cut into 256-byte aligned parts; the context's workspace
-    // and retained result (fdf_fetch_last) are not touched
-    const uint64_t o_smooth = align256(frame_bytes);
-    const uint64_t o_pts = o_smooth + (smooth ? align256(frame_bytes) : 0);
-    const uint64_t o_offs = o_pts + align256(n_points * sizeof(fdf_point));
-    const uint64_t o_ang = o_offs + 256;
-    const uint64_t o_table = o_ang + (angles ? align256(n_points * sizeof(float)) : 0);
-    const uint64_t o_desc = o_table + align256(table_bytes);
-    const uint64_t bytes = o_desc + align256(n_points * (uint64_t)fdfk::kBriefBytes);
-    std::lock_guard<std::mutex> lock(ctx->mu);    // the context's stream carries the call
-    DeviceGuard guard(ctx->device);
-    uint8_t* d = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&d), bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return FDF_ERR_ALLOC;
-    }
-    const uint64_t one_frame[2] = {0, n_points};
-    hipStream_t s = ctx->stream;
-    hipError_t e = stride_bytes == width
-                       ? hipMemcpyAsync(d, data, frame_bytes, hipMemcpyHostToDevice, s)
-                       : hipMemcpy2DAsync(d, width, data, stride_bytes, width, height,
-                                          hipMemcpyHostToDevice, s);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(d + o_pts, points, n_points * sizeof(fdf_point), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(d + o_offs, one_frame, sizeof(one_frame), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && angles)
-        e = hipMemcpyAsync(d + o_ang, angles, n_points * sizeof(float), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(d + o_table, table.data(), table_bytes, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && smooth)
-        e = smooth_enqueue(d, 1, width, height, frame_bytes, d + o_smooth, frame_bytes, s);
-    if (e == hipSuccess)
-        e = describe_enqueue(smooth ? d + o_smooth : d, 1, width, height, frame_bytes,
-                             reinterpret_cast<const fdf_point*>(d + o_pts), n_points,
-                             reinterpret_cast<const uint64_t*>(d + o_offs),
-                             angles ? reinterpret_cast<const float*>(d + o_ang) : nullptr,
-                             reinterpret_cast<const int8_t*>(d + o_table), n_bins, d + o_desc, s);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(out_desc, d + o_desc, n_points * (uint64_t)fdfk::kBriefBytes,
-                           hipMemcpyDeviceToHost, s);
-    const hipError_t se = hipStreamSynchronize(s);     // nothing may still use `d`
-    if (e == hipSuccess) e = se;
-    (void)hipFree(d);
     return e == hipSuccess ? FDF_OK : FDF_ERR_DEVICE;
 }
 

@@ -1,6 +1,7 @@
-// fdf_common.h -- device helpers of the FAST kernels (fdf_sweep.hip, fdf_kernels.hip):
-// circle geometry, byte-SWAR comparisons, wave ballots, the per-lane segment test and the
-// two NMS score functions of the reference (iwanders/feature_detector_fast).
+// fdf_common.h -- device helpers of every kernel file: a frame's index range, a workgroup's
+// share of it and raw buffer resources (fdf_select.hip, fdf_orient.hip, fdf_describe.hip);
+// circle geometry, byte-SWAR comparisons, wave ballots, the per-lane segment test and the two
+// NMS score functions of the reference (fdf_sweep.hip, fdf_kernels.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -8,6 +9,35 @@
 #include "fdf_kernels.h"
 
 namespace fdfk {
+
+// Point lists: the points of the frames concatenated, frame f = [offs[f], min(offs[f+1], cap)).
+struct IndexRange { uint64_t lo, hi; };
+
+// Frame f's range, clamped to `cap` and ordered (hi >= lo) whatever the offsets hold.
+__device__ __forceinline__ IndexRange frame_range(const uint64_t* offs, uint64_t cap, uint32_t f) {
+    const uint64_t b = min(offs[f], cap);
+    uint64_t e = min(offs[f + 1], cap);
+    if (e < b) e = b;
+    return {b, e};
+}
+
+// The contiguous share of [b, e) that workgroup `chunk` of `chunks` takes, in whole passes of
+// `per_pass` points: the shares tile [b, e) in chunk order, the last ones possibly empty.
+__host__ __device__ inline IndexRange wg_share(uint64_t b, uint64_t e, uint32_t chunk,
+                                               uint32_t chunks, uint32_t per_pass) {
+    uint64_t per = ((e - b) + chunks - 1) / chunks;
+    per = (per + per_pass - 1) / per_pass * per_pass;
+    const uint64_t lo = b + chunk * per < e ? b + chunk * per : e;
+    return {lo, lo + per < e ? lo + per : e};
+}
+
+// Word 3 of a raw buffer resource on gfx9: DATA_FORMAT = 32 (bits 15-18 = 4), no swizzle, no
+// typed conversion.  Loads and stores past `bytes` return 0 and touch no memory.
+constexpr int kRawBufferWord3 = 0x00020000;
+template <typename T>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t frame_rsrc(const T* base, int bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(base), 0, bytes, kRawBufferWord3);
+}
 
 // ---------------------------------------------------------------------------------------
 // Circle geometry: src/fast_simd.rs:79-98 (index 0 = north, clockwise).

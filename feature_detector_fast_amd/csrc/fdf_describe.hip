@@ -48,20 +48,13 @@ typedef uint64_t __attribute__((aligned(1))) u64_unaligned;
 __global__ __launch_bounds__(kDescribeThreads) void describe_kernel(DescribeParams P) {
     constexpr uint32_t kPerPass = kDescribeThreads / 64;  // keypoints of a workgroup pass
     const uint32_t f = blockIdx.y;
-    const uint64_t b = min(P.offs[f], P.cap);
-    uint64_t e = min(P.offs[f + 1], P.cap);
-    if (e < b) e = b;
-    // this workgroup's contiguous share of [b, e), in whole passes
-    uint64_t per = ((e - b) + gridDim.x - 1) / gridDim.x;
-    per = (per + kPerPass - 1) / kPerPass * kPerPass;
-    const uint64_t lo = min(b + blockIdx.x * per, e), hi = min(lo + per, e);
+    const IndexRange fr = frame_range(P.offs, P.cap, f);
+    const auto [lo, hi] = wg_share(fr.lo, fr.hi, blockIdx.x, gridDim.x, kPerPass);
     if (lo == hi) return;
 
     const int W = (int)P.width, H = (int)P.height;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint8_t*>(P.frames + (uint64_t)f * P.frame_stride), 0, W * H, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<int8_t*>(P.table), 0, (int)(P.n_bins * kBriefTableBytes), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = frame_rsrc(P.frames + (uint64_t)f * P.frame_stride, W * H);
+    const __amdgpu_buffer_rsrc_t rt = frame_rsrc(P.table, (int)(P.n_bins * kBriefTableBytes));
     const int lane = (int)(threadIdx.x % 64);
 
     uint64_t i = lo + threadIdx.x / 64;                   // uniform over a wave
@@ -128,10 +121,8 @@ __global__ __launch_bounds__(kSmoothThreads) void smooth_kernel(SmoothParams P) 
     const uint32_t strip = gid / P.groups, g = gid % P.groups;
     if (strip >= P.strips) return;
     const int W = (int)P.width, H = (int)P.height;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint8_t*>(P.frames + (uint64_t)f * P.frame_stride), 0, W * H, 0x00020000);
-    const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(
-        P.out + (uint64_t)f * P.out_stride, 0, W * H, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = frame_rsrc(P.frames + (uint64_t)f * P.frame_stride, W * H);
+    const __amdgpu_buffer_rsrc_t ro = frame_rsrc(P.out + (uint64_t)f * P.out_stride, W * H);
     // the last group of a width that is no multiple of 4 moves left onto its neighbour (both
     // write the same values there), so every thread stores whole dwords
     const int x0 = min(4 * (int)g, W - 4);
@@ -189,10 +180,8 @@ __global__ __launch_bounds__(kSmoothThreads) void smooth_small_kernel(SmoothPara
     const uint32_t gid = blockIdx.x * kSmoothThreads + threadIdx.x;
     const int W = (int)P.width, H = (int)P.height;
     if (gid >= P.width * P.height) return;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint8_t*>(P.frames + (uint64_t)f * P.frame_stride), 0, W * H, 0x00020000);
-    const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(
-        P.out + (uint64_t)f * P.out_stride, 0, W * H, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = frame_rsrc(P.frames + (uint64_t)f * P.frame_stride, W * H);
+    const __amdgpu_buffer_rsrc_t ro = frame_rsrc(P.out + (uint64_t)f * P.out_stride, W * H);
     const int x = (int)(gid % P.width), y = (int)(gid / P.width);
     uint32_t s = 12;
     for (int dy = -2; dy <= 2; ++dy)
@@ -206,8 +195,8 @@ __global__ __launch_bounds__(kSmoothThreads) void smooth_small_kernel(SmoothPara
 
 hipError_t launch_describe(const DescribeParams& p, uint32_t chunks, hipStream_t stream) {
     if (p.n_frames == 0 || p.cap == 0) return hipSuccess;
-    if (p.n_frames > 65535u || chunks == 0 || p.n_bins == 0 || p.n_bins > kBriefMaxBins ||
-        p.width == 0 || p.height == 0 || (uint64_t)p.width * p.height > kOrientMaxPixels)
+    if (!frames_fit_launch(p.n_frames, p.width, p.height) || chunks == 0 || p.n_bins == 0 ||
+        p.n_bins > kBriefMaxBins)
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(describe_kernel, dim3(chunks, p.n_frames), dim3(kDescribeThreads), 0,
                        stream, p);
@@ -216,8 +205,7 @@ hipError_t launch_describe(const DescribeParams& p, uint32_t chunks, hipStream_t
 
 hipError_t launch_smooth(const SmoothParams& p, hipStream_t stream) {
     if (p.n_frames == 0) return hipSuccess;
-    if (p.n_frames > 65535u || p.width == 0 || p.height == 0 || p.strip_rows == 0 ||
-        (uint64_t)p.width * p.height > kOrientMaxPixels ||
+    if (!frames_fit_launch(p.n_frames, p.width, p.height) || p.strip_rows == 0 ||
         p.groups != (p.width + 3) / 4 ||
         p.strips != (p.height + p.strip_rows - 1) / p.strip_rows)
         return hipErrorInvalidValue;

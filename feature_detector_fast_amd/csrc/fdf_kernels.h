@@ -1,6 +1,6 @@
 // fdf_kernels.h -- shared between the HIP kernels (fdf_sweep.hip, fdf_kernels.hip,
-// fdf_select.hip, fdf_orient.hip, fdf_describe.hip) and the C-ABI host layer (fdf_api.cpp):
-// geometry constants, LDS layout and launch parameters.
+// fdf_select.hip, fdf_orient.hip, fdf_describe.hip) and the C-ABI host layer (fdf_api.cpp,
+// fdf_stages.cpp): geometry constants, LDS layout and launch parameters.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -286,6 +286,11 @@ hipError_t launch_select(const SelectParams& p, hipStream_t stream);
 constexpr int kOrientThreads = 256;
 constexpr uint32_t kOrientMaxRadius = 31;             // window of 2 r + 1 <= 64 bytes
 constexpr uint64_t kOrientMaxPixels = 0x7fffff00ull;  // byte offsets of a frame fit an int
+// launch_orient, launch_describe, launch_smooth: grid.y = n_frames, a frame an int can index
+inline bool frames_fit_launch(uint32_t n_frames, uint32_t width, uint32_t height) {
+    return n_frames <= 65535u && width != 0 && height != 0 &&
+           (uint64_t)width * height <= kOrientMaxPixels;
+}
 struct OrientParams {
     const uint8_t* frames;       // frame f at frames + f * frame_stride, width * height bytes
     uint64_t frame_stride;

@@ -217,10 +217,8 @@ __global__ __launch_bounds__(256) void rgb_to_luma_kernel(const uint8_t* rgb,
             dst[i] = (uint8_t)luma_of(src[3 * i], src[3 * i + 1], src[3 * i + 2]);
         return;
     }
-    const __amdgpu_buffer_rsrc_t in = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint8_t*>(src), 0, (int)(3u * pixels), 0x00020000);
-    const __amdgpu_buffer_rsrc_t out = __builtin_amdgcn_make_buffer_rsrc(dst, 0, (int)pixels,
-                                                                          0x00020000);
+    const __amdgpu_buffer_rsrc_t in = frame_rsrc(src, (int)(3u * pixels));
+    const __amdgpu_buffer_rsrc_t out = frame_rsrc(dst, (int)pixels);
     uint32_t w[12];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {

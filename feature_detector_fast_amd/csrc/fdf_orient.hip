@@ -68,18 +68,12 @@ template <int L>
 __global__ __launch_bounds__(kOrientThreads) void orient_kernel(OrientParams P) {
     constexpr uint32_t kPerPass = kOrientThreads / L;     // keypoints of a workgroup pass
     const uint32_t f = blockIdx.y;
-    const uint64_t b = min(P.offs[f], P.cap);
-    uint64_t e = min(P.offs[f + 1], P.cap);
-    if (e < b) e = b;
-    // this workgroup's contiguous share of [b, e), in whole passes
-    uint64_t per = ((e - b) + gridDim.x - 1) / gridDim.x;
-    per = (per + kPerPass - 1) / kPerPass * kPerPass;
-    const uint64_t lo = min(b + blockIdx.x * per, e), hi = min(lo + per, e);
+    const IndexRange fr = frame_range(P.offs, P.cap, f);
+    const auto [lo, hi] = wg_share(fr.lo, fr.hi, blockIdx.x, gridDim.x, kPerPass);
     if (lo == hi) return;
 
     const int W = (int)P.width, H = (int)P.height, r = (int)P.radius;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint8_t*>(P.frames + (uint64_t)f * P.frame_stride), 0, W * H, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = frame_rsrc(P.frames + (uint64_t)f * P.frame_stride, W * H);
     const int j = (int)(threadIdx.x % L);                 // the lane's dword of the window
     const uint32_t wts = (uint32_t)(4 * j) * 0x01010101u + 0x03020100u;   // bytes d + r
     const int j8 = 32 * j - 8 * r;                        // row_mask
@@ -143,8 +137,8 @@ __global__ __launch_bounds__(kOrientThreads) void orient_kernel(OrientParams P) 
 
 hipError_t launch_orient(const OrientParams& p, uint32_t chunks, hipStream_t stream) {
     if (p.n_frames == 0 || p.cap == 0) return hipSuccess;
-    if (p.n_frames > 65535u || chunks == 0 || p.radius == 0 || p.radius > kOrientMaxRadius ||
-        p.width == 0 || p.height == 0 || (uint64_t)p.width * p.height > kOrientMaxPixels)
+    if (!frames_fit_launch(p.n_frames, p.width, p.height) || chunks == 0 || p.radius == 0 ||
+        p.radius > kOrientMaxRadius)
         return hipErrorInvalidValue;
     const dim3 grid(chunks, p.n_frames), block(kOrientThreads);
     if (p.radius <= 3)

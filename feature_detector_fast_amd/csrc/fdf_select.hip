@@ -109,9 +109,7 @@ __global__ __launch_bounds__(kSelThreads) void select_kernel(SelectParams P) {
     const uint32_t r = blockIdx.x, f = blockIdx.y;
     const uint64_t row = (uint64_t)f * P.rows + r;
 
-    const uint64_t b = min(P.offs[f], P.cap);
-    uint64_t e = min(P.offs[f + 1], P.cap);
-    if (e < b) e = b;
+    const auto [b, e] = frame_range(P.offs, P.cap, f);
     // the cell row's points: y in [r * ch, (r + 1) * ch); the first row starts at the frame's
     // first point and the last ends at its last, so the rows' ranges tile [b, e)
     uint64_t lo = r == 0 ? b : lower_bound_y(P.pts, b, e, (uint64_t)r * P.ch);

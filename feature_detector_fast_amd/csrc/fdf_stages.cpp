@@ -1,0 +1,553 @@
+// fdf_stages.cpp -- the C ABI of the stages behind the detector (extensions: the reference
+// returns points only): best-K selection, orientation, steered BRIEF descriptors and box
+// smoothing.  Each has an asynchronous _device entry on the caller's stream and memory and a
+// host convenience _points entry.  Of a context they use the device, the mutex and the
+// stream only: its workspace and retained result (fdf_fetch_last) are not touched.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "fdf_ctx.h"
+
+namespace {
+
+// One device allocation for a _points call, cut into 256-byte aligned parts.  In order:
+// declare the parts, open(), transfers and kernels on the context's stream (which carries the
+// call: its mutex is held and its device current while the arena lives), close().  The first
+// error of a transfer or kernel is kept and skips the transfers after it.
+class Arena {
+public:
+    template <typename T>
+    struct Part { uint64_t offset, count; };
+
+    explicit Arena(fdf_ctx* ctx) : ctx_(ctx), lock_(ctx->mu), guard_(ctx->device) {}
+    ~Arena() { (void)close(); }
+
+    template <typename T>
+    Part<T> part(uint64_t count) {    // a size no allocation can have makes open() fail
+        const Part<T> p{bytes_, count};
+        bytes_ = count > (~0ull - bytes_ - 256u) / sizeof(T) ? ~0ull - 256u
+                                                             : bytes_ + align256(count * sizeof(T));
+        return p;
+    }
+    int open() {
+        if (hipMalloc(reinterpret_cast<void**>(&d_), bytes_) == hipSuccess) return FDF_OK;
+        (void)hipGetLastError();
+        d_ = nullptr;
+        return FDF_ERR_ALLOC;
+    }
+    template <typename T>
+    T* at(Part<T> p) const { return reinterpret_cast<T*>(d_ + p.offset); }
+    bool ok() const { return e_ == hipSuccess; }
+    void note(hipError_t e) { if (ok()) e_ = e; }
+    template <typename T>
+    void upload(Part<T> p, const T* src) {
+        if (ok()) e_ = hipMemcpyAsync(at(p), src, p.count * sizeof(T), hipMemcpyHostToDevice, ctx_->stream);
+    }
+    template <typename T>
+    void download(T* dst, Part<T> p, uint64_t count) {
+        if (ok()) e_ = hipMemcpyAsync(dst, at(p), count * sizeof(T), hipMemcpyDeviceToHost, ctx_->stream);
+    }
+    // a frame whose rows lie `stride_bytes` apart, packed on the device
+    void upload_frame(Part<uint8_t> p, const uint8_t* data, uint32_t width, uint32_t height,
+                      size_t stride_bytes) {
+        if (!ok()) return;
+        e_ = stride_bytes == width
+                 ? hipMemcpyAsync(at(p), data, p.count, hipMemcpyHostToDevice, ctx_->stream)
+                 : hipMemcpy2DAsync(at(p), width, data, stride_bytes, width, height,
+                                    hipMemcpyHostToDevice, ctx_->stream);
+    }
+    void upload_one_frame(Part<uint64_t> p, uint64_t n_points) {    // offsets {0, n_points}
+        one_frame_[1] = n_points;
+        upload(p, one_frame_);
+    }
+    // Drains the stream (nothing may still use the allocation) and frees; FDF_ERR_DEVICE
+    // after any failed transfer or kernel.
+    int close() {
+        if (d_) {
+            note(hipStreamSynchronize(ctx_->stream));
+            (void)hipFree(d_);
+            d_ = nullptr;
+        }
+        return ok() ? FDF_OK : FDF_ERR_DEVICE;
+    }
+
+private:
+    fdf_ctx* ctx_;
+    std::lock_guard<std::mutex> lock_;
+    DeviceGuard guard_;
+    uint8_t* d_ = nullptr;
+    uint64_t bytes_ = 0;
+    hipError_t e_ = hipSuccess;
+    uint64_t one_frame_[2] = {0, 0};    // an asynchronous copy's source: lives as long as the call
+};
+
+bool points_inside(const fdf_point* points, size_t n_points, uint32_t width, uint32_t height) {
+    for (size_t k = 0; k < n_points; ++k)
+        if (points[k].x >= width || points[k].y >= height) return false;
+    return true;
+}
+
+// Frames of a _device entry lie `stride_bytes` apart; a single frame's stride is not looked at.
+inline uint64_t frame_stride(uint32_t n_frames, uint64_t stride_bytes, uint64_t frame_bytes) {
+    return n_frames > 1 ? stride_bytes : frame_bytes;
+}
+
+// What fdf_orient_device and fdf_describe_device check after their own parameters.  *todo is
+// clear when the call is valid and has nothing to enqueue; otherwise *stride is the frames'.
+inline int check_point_frames(uint32_t n_frames, uint32_t width, uint32_t height, uint64_t cap,
+                              uint64_t stride_bytes, bool have_ptrs, uint64_t* stride, bool* todo) {
+    *todo = false;
+    int empty = 0;
+    const int rc = check_shape(width, height, &empty);
+    if (rc) return rc;
+    if (empty || n_frames == 0 || cap == 0) return FDF_OK;
+    if (!have_ptrs) return FDF_ERR_ARG;
+    const uint64_t frame_bytes = (uint64_t)width * height;
+    if (frame_bytes > fdfk::kOrientMaxPixels) return FDF_ERR_SIZE;
+    *stride = frame_stride(n_frames, stride_bytes, frame_bytes);
+    *todo = *stride >= frame_bytes;
+    return *todo ? FDF_OK : FDF_ERR_ARG;
+}
+
+// Workgroups per frame of a point-list kernel: about `per_wg` points each at the detector's
+// usual density, `max_chunks` at most.
+inline uint32_t chunks_per_frame(uint64_t cap, uint32_t n_frames, uint32_t width, uint32_t height,
+                                 uint32_t per_wg, uint32_t max_chunks) {
+    const uint64_t est = std::min<uint64_t>(cap, (uint64_t)width * height / 32 * n_frames);
+    return (uint32_t)std::min<uint64_t>(max_chunks, est / n_frames / per_wg + 1);
+}
+
+inline int status_of(hipError_t e) { return e == hipSuccess ? FDF_OK : FDF_ERR_DEVICE; }
+
+}  // namespace
+
+extern "C" {
+
+// ---- best-K selection per grid cell (fdf_select.hip) -------------------------------------
+namespace {
+
+// Scratch of one fdf_select_device call, every part 256-byte aligned: the per-frame kept
+// totals (zeroed on the stream before the kernels), the kept count and the index range of
+// every (frame, cell row), and `cap` keep flags for a caller that passes no d_keep.
+struct SelectLayout {
+    uint32_t cw = 0, ch = 0, cells_x = 0, rows = 0;
+    uint64_t frame_tot = 0, row_cnt = 0, row_range = 0, keep = 0, total = 0;
+};
+
+// FDF_OK with *empty set for shapes with no keypoints; the shape's error otherwise.
+int select_layout(uint32_t n_frames, uint32_t width, uint32_t height, uint32_t cell_w,
+                  uint32_t cell_h, uint64_t cap, SelectLayout* L, int* empty) {
+    int rc = check_shape(width, height, empty);
+    if (rc) return rc;
+    if (n_frames > 65535u || (uint64_t)width * height > 0xffffffffull) return FDF_ERR_ARG;
+    if (n_frames == 0) *empty = 1;
+    if (*empty) return FDF_OK;
+    L->cw = cell_w == 0 || cell_w > width ? width : cell_w;
+    L->ch = cell_h == 0 || cell_h > height ? height : cell_h;
+    L->cells_x = (width + L->cw - 1) / L->cw;
+    L->rows = (height + L->ch - 1) / L->ch;
+    if (L->rows > fdfk::kSelMaxRows) return FDF_ERR_ARG;
+    const uint64_t nrows = (uint64_t)n_frames * L->rows;
+    L->frame_tot = 0;
+    L->row_cnt = align256(sizeof(uint64_t) * n_frames);
+    L->row_range = L->row_cnt + align256(sizeof(uint32_t) * nrows);
+    L->keep = L->row_range + align256(2 * sizeof(uint64_t) * nrows);
+    if (cap > ~0ull - L->keep - 256u) return FDF_ERR_ARG;
+    L->total = L->keep + align256(cap);
+    return FDF_OK;
+}
+
+}  // namespace
+
+int fdf_select_scratch_bytes(uint32_t n_frames, uint32_t width, uint32_t height,
+                             uint32_t cell_w, uint32_t cell_h, uint64_t cap, uint64_t* bytes) {
+    if (!bytes) return FDF_ERR_ARG;
+    SelectLayout L;
+    int empty = 0;
+    const int rc = select_layout(n_frames, width, height, cell_w, cell_h, cap, &L, &empty);
+    if (rc) return rc;
+    *bytes = empty ? 0 : L.total;
+    return FDF_OK;
+}
+
+int fdf_select_device(fdf_ctx* ctx, uint32_t n_frames, uint32_t width, uint32_t height,
+                      const fdf_point* d_points, const uint16_t* d_scores, uint64_t cap,
+                      const uint64_t* d_frame_offsets, uint32_t cell_w, uint32_t cell_h,
+                      uint32_t k, fdf_point* d_sel, uint16_t* d_sel_scores, uint64_t sel_cap,
+                      uint64_t* d_sel_offsets, uint8_t* d_keep, void* d_scratch,
+                      uint64_t scratch_bytes, void* stream) {
+    if (!ctx || !d_sel_offsets || k == 0) return FDF_ERR_ARG;
+    SelectLayout L;
+    int empty = 0;
+    const int rc = select_layout(n_frames, width, height, cell_w, cell_h, cap, &L, &empty);
+    if (rc) return rc;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);   // NULL = the HIP null stream
+    if (!empty) {
+        if (!d_frame_offsets || !d_scratch || scratch_bytes < L.total ||
+            ((uintptr_t)d_scratch & 255u) != 0)
+            return FDF_ERR_ARG;
+        if (cap && (!d_points || !d_scores)) return FDF_ERR_ARG;
+        if (sel_cap && (!d_sel || !d_sel_scores)) return FDF_ERR_ARG;
+    }
+    DeviceGuard guard(ctx->device);
+    if (empty || cap == 0)
+        return status_of(hipMemsetAsync(d_sel_offsets, 0, sizeof(uint64_t) * (n_frames + 1ull), s));
+    uint8_t* base = static_cast<uint8_t*>(d_scratch);
+    fdfk::SelectParams p{};
+    p.pts = reinterpret_cast<const uint2*>(d_points);
+    p.scores = d_scores;
+    p.offs = d_frame_offsets;
+    p.cap = cap;
+    p.n_frames = n_frames;
+    p.cw = L.cw;
+    p.ch = L.ch;
+    p.cells_x = L.cells_x;
+    p.rows = L.rows;
+    p.k = k;
+    p.keep = d_keep ? d_keep : base + L.keep;
+    p.frame_tot = reinterpret_cast<uint64_t*>(base + L.frame_tot);
+    p.row_cnt = reinterpret_cast<uint32_t*>(base + L.row_cnt);
+    p.row_range = reinterpret_cast<uint64_t*>(base + L.row_range);
+    p.sel = reinterpret_cast<uint2*>(d_sel);
+    p.sel_scores = d_sel_scores;
+    p.sel_cap = sel_cap;
+    p.sel_offs = d_sel_offsets;
+    // the frame totals are summed into; the keep flags of indices no frame owns stay 0
+    hipError_t e = hipMemsetAsync(p.frame_tot, 0, sizeof(uint64_t) * n_frames, s);
+    if (e == hipSuccess) e = hipMemsetAsync(p.keep, 0, cap, s);
+    if (e == hipSuccess) e = fdfk::launch_select(p, s);
+    return status_of(e);
+}
+
+int fdf_select_points(fdf_ctx* ctx, const fdf_point* points, const uint16_t* scores,
+                      const uint64_t* frame_offsets, uint32_t n_frames, size_t n_points,
+                      uint32_t width, uint32_t height, uint32_t cell_w, uint32_t cell_h,
+                      uint32_t k, fdf_point* out, uint16_t* out_scores, size_t cap,
+                      uint64_t* out_offsets, size_t* n_out) {
+    if (!ctx || !n_out || k == 0) return FDF_ERR_ARG;
+    if (n_points && (!points || !scores)) return FDF_ERR_ARG;
+    if (cap && (!out || !out_scores)) return FDF_ERR_ARG;
+    if (!frame_offsets && n_frames != 1) return FDF_ERR_ARG;
+    SelectLayout L;
+    int empty = 0;
+    const int rc = select_layout(n_frames, width, height, cell_w, cell_h, n_points, &L, &empty);
+    if (rc) return rc;
+    *n_out = 0;
+    const uint64_t noffs = n_frames + 1ull;
+    if (empty || n_points == 0) {
+        if (out_offsets) std::memset(out_offsets, 0, sizeof(uint64_t) * noffs);
+        return FDF_OK;
+    }
+    Arena a(ctx);
+    const auto d_pts = a.part<fdf_point>(n_points);
+    const auto d_scores = a.part<uint16_t>(n_points);
+    const auto d_offs = a.part<uint64_t>(noffs);
+    const auto d_sel = a.part<fdf_point>(cap);
+    const auto d_sel_scores = a.part<uint16_t>(cap);
+    const auto d_sel_offs = a.part<uint64_t>(noffs);
+    const auto d_scratch = a.part<uint8_t>(L.total);
+    if (a.open() != FDF_OK) return FDF_ERR_ALLOC;
+    a.upload(d_pts, points);
+    a.upload(d_scores, scores);
+    if (frame_offsets) a.upload(d_offs, frame_offsets);
+    else a.upload_one_frame(d_offs, n_points);
+    if (a.ok()) {
+        const int status = fdf_select_device(
+            ctx, n_frames, width, height, a.at(d_pts), a.at(d_scores), n_points, a.at(d_offs),
+            cell_w, cell_h, k, a.at(d_sel), a.at(d_sel_scores), cap, a.at(d_sel_offs), nullptr,
+            a.at(d_scratch), L.total, ctx->stream);
+        if (status != FDF_OK) return status;
+    }
+    // two phases: the offsets tell how many points to copy
+    std::vector<uint64_t> offs(noffs);
+    a.download(offs.data(), d_sel_offs, noffs);
+    a.note(hipStreamSynchronize(ctx->stream));
+    const uint64_t total = a.ok() ? offs[n_frames] : 0;
+    const uint64_t ncopy = std::min<uint64_t>(total, cap);
+    if (ncopy) {
+        a.download(out, d_sel, ncopy);
+        a.download(out_scores, d_sel_scores, ncopy);
+    }
+    if (a.close() != FDF_OK) return FDF_ERR_DEVICE;
+    *n_out = (size_t)total;
+    if (out_offsets) std::memcpy(out_offsets, offs.data(), noffs * sizeof(uint64_t));
+    return total > cap ? FDF_ERR_CAPACITY : FDF_OK;
+}
+
+// ---- orientation by intensity centroid (fdf_orient.hip) ---------------------------------
+
+int fdf_orient_disc(uint32_t radius, uint8_t* half_widths) {
+    if (radius == 0 || radius > fdfk::kOrientMaxRadius || !half_widths) return FDF_ERR_ARG;
+    // OpenCV's umax: the rounded circle for the rows up to r / sqrt(2), mirrored for the rest
+    // so that the disc is symmetric about its diagonal
+    const int r = (int)radius;
+    const int vmax = (int)std::floor(r * std::sqrt(2.0) / 2 + 1);
+    const int vmin = (int)std::ceil(r * std::sqrt(2.0) / 2);
+    int u[fdfk::kOrientMaxRadius + 2] = {0};
+    for (int v = 0; v <= vmax; ++v)
+        u[v] = (int)std::floor(std::sqrt((double)r * r - (double)v * v) + 0.5);
+    for (int v = r, v0 = 0; v >= vmin; --v) {
+        while (u[v0] == u[v0 + 1]) ++v0;
+        u[v] = v0;
+        ++v0;
+    }
+    for (int v = 0; v <= r; ++v) half_widths[v] = (uint8_t)u[v];
+    return FDF_OK;
+}
+
+namespace {
+
+// The launch of fdf_orient_device / fdf_orient_points (arguments already validated).
+hipError_t orient_enqueue(const uint8_t* d_frames, uint32_t n_frames, uint32_t width,
+                          uint32_t height, uint64_t frame_stride, const fdf_point* d_points,
+                          uint64_t cap, const uint64_t* d_offsets, uint32_t radius,
+                          float* d_angles, int32_t* d_moments, hipStream_t s) {
+    fdfk::OrientParams p{};
+    p.frames = d_frames;
+    p.frame_stride = frame_stride;
+    p.pts = reinterpret_cast<const uint2*>(d_points);
+    p.offs = d_offsets;
+    p.cap = cap;
+    p.n_frames = n_frames;
+    p.width = width;
+    p.height = height;
+    p.radius = radius;
+    p.angles = d_angles;
+    p.moments = d_moments;
+    if (fdf_orient_disc(radius, p.u) != FDF_OK) return hipErrorInvalidValue;
+    return fdfk::launch_orient(p, chunks_per_frame(cap, n_frames, width, height, 256, 256), s);
+}
+
+}  // namespace
+
+int fdf_orient_device(fdf_ctx* ctx, const uint8_t* d_frames, uint32_t n_frames, uint32_t width,
+                      uint32_t height, uint64_t frame_stride_bytes, const fdf_point* d_points,
+                      uint64_t cap, const uint64_t* d_frame_offsets, uint32_t radius,
+                      float* d_angles, int32_t* d_moments, void* stream) {
+    if (!ctx || !d_frame_offsets || radius == 0 || radius > fdfk::kOrientMaxRadius ||
+        n_frames > 65535u)
+        return FDF_ERR_ARG;
+    uint64_t fs = 0;
+    bool todo = false;
+    const int rc = check_point_frames(n_frames, width, height, cap, frame_stride_bytes,
+                                      d_frames && d_points && d_angles, &fs, &todo);
+    if (!todo) return rc;
+    DeviceGuard guard(ctx->device);
+    return status_of(orient_enqueue(d_frames, n_frames, width, height, fs, d_points, cap,
+                                    d_frame_offsets, radius, d_angles, d_moments,
+                                    reinterpret_cast<hipStream_t>(stream)));
+}
+
+int fdf_orient_points(fdf_ctx* ctx, const uint8_t* data, uint32_t width, uint32_t height,
+                      size_t stride_bytes, const fdf_point* points, size_t n_points,
+                      uint32_t radius, float* out_angles, int32_t* out_moments) {
+    if (!ctx || radius == 0 || radius > fdfk::kOrientMaxRadius) return FDF_ERR_ARG;
+    if (n_points && (!points || !out_angles || !data)) return FDF_ERR_ARG;
+    if (stride_bytes < width) return FDF_ERR_ARG;
+    if (!points_inside(points, n_points, width, height)) return FDF_ERR_ARG;
+    if (n_points == 0) return FDF_OK;
+    const uint64_t frame_bytes = (uint64_t)width * height;
+    if (frame_bytes > fdfk::kOrientMaxPixels) return FDF_ERR_SIZE;
+    Arena a(ctx);
+    const auto d_frame = a.part<uint8_t>(frame_bytes);
+    const auto d_pts = a.part<fdf_point>(n_points);
+    const auto d_offs = a.part<uint64_t>(2);
+    const auto d_ang = a.part<float>(n_points);
+    const auto d_mom = a.part<int32_t>(out_moments ? 2 * (uint64_t)n_points : 0);
+    if (a.open() != FDF_OK) return FDF_ERR_ALLOC;
+    a.upload_frame(d_frame, data, width, height, stride_bytes);
+    a.upload(d_pts, points);
+    a.upload_one_frame(d_offs, n_points);
+    if (a.ok())
+        a.note(orient_enqueue(a.at(d_frame), 1, width, height, frame_bytes, a.at(d_pts), n_points,
+                              a.at(d_offs), radius, a.at(d_ang),
+                              out_moments ? a.at(d_mom) : nullptr, ctx->stream));
+    a.download(out_angles, d_ang, n_points);
+    if (out_moments) a.download(out_moments, d_mom, d_mom.count);
+    return a.close();
+}
+
+// ---- steered BRIEF descriptors and box smoothing (fdf_describe.hip) -----------------------
+
+int fdf_brief_pattern(int8_t pattern[1024]) {
+    if (!pattern) return FDF_ERR_ARG;
+    uint32_t s = 0x9E3779B9u;
+    auto next = [&s]() {
+        s ^= s << 13;
+        s ^= s >> 17;
+        s ^= s << 5;
+        return s;
+    };
+    auto coord = [&next]() {              // bell-shaped in -21..21
+        int v = -21;
+        for (int k = 0; k < 6; ++k) v += (int)(next() >> 29);
+        return v;
+    };
+    uint32_t n = 0;
+    while (n < fdfk::kBriefTests) {
+        int t[4];
+        for (int& v : t) v = coord();
+        if (t[0] * t[0] + t[1] * t[1] > 13 * 13 || t[2] * t[2] + t[3] * t[3] > 13 * 13) continue;
+        if (t[0] == t[2] && t[1] == t[3]) continue;
+        bool seen = false;
+        for (uint32_t k = 0; k < n && !seen; ++k)
+            seen = pattern[4 * k] == t[0] && pattern[4 * k + 1] == t[1] &&
+                   pattern[4 * k + 2] == t[2] && pattern[4 * k + 3] == t[3];
+        if (seen) continue;
+        for (int k = 0; k < 4; ++k) pattern[4 * n + k] = (int8_t)t[k];
+        ++n;
+    }
+    return FDF_OK;
+}
+
+int fdf_brief_steer(const int8_t* pattern, uint32_t n_bins, int8_t* table) {
+#pragma clang fp contract(off)
+    if (!pattern || !table || n_bins == 0 || n_bins > fdfk::kBriefMaxBins) return FDF_ERR_ARG;
+    // double products and sums, one rounding to float, then half away from zero
+    auto quantise = [](double v) {
+        const float r = std::round((float)v);
+        return (int8_t)std::min(std::max(r, -128.0f), 127.0f);
+    };
+    for (uint32_t b = 0; b < n_bins; ++b) {
+        const double theta = 2 * M_PI * b / n_bins;
+        const double c = std::cos(theta), s = std::sin(theta);
+        int8_t* row = table + (size_t)b * fdfk::kBriefTableBytes;
+        for (uint32_t k = 0; k < 2 * fdfk::kBriefTests; ++k) {    // points (x, y), y pointing down
+            const double x = pattern[2 * k], y = pattern[2 * k + 1];
+            const double xc = x * c, ys = y * s, xs = x * s, yc = y * c;
+            row[2 * k] = quantise(xc - ys);
+            row[2 * k + 1] = quantise(xs + yc);
+        }
+    }
+    return FDF_OK;
+}
+
+namespace {
+
+hipError_t smooth_enqueue(const uint8_t* d_frames, uint32_t n_frames, uint32_t width,
+                          uint32_t height, uint64_t frame_stride, uint8_t* d_out,
+                          uint64_t out_stride, hipStream_t s) {
+    fdfk::SmoothParams p{};
+    p.frames = d_frames;
+    p.frame_stride = frame_stride;
+    p.out = d_out;
+    p.out_stride = out_stride;
+    p.n_frames = n_frames;
+    p.width = width;
+    p.height = height;
+    p.groups = (width + 3) / 4;
+    // the tallest strips (4 halo rows read per strip) that still leave 16 waves per CU
+    p.strip_rows = fdfk::kSmoothStripRows;
+    while (p.strip_rows > 8 &&
+           (uint64_t)p.groups * ((height + p.strip_rows - 1) / p.strip_rows) * n_frames < 256 * 1024)
+        p.strip_rows /= 2;
+    p.strips = (height + p.strip_rows - 1) / p.strip_rows;
+    return fdfk::launch_smooth(p, s);
+}
+
+// The launch of fdf_describe_device / fdf_describe_points (arguments already validated).
+hipError_t describe_enqueue(const uint8_t* d_frames, uint32_t n_frames, uint32_t width,
+                            uint32_t height, uint64_t frame_stride, const fdf_point* d_points,
+                            uint64_t cap, const uint64_t* d_offsets, const float* d_angles,
+                            const int8_t* d_table, uint32_t n_bins, uint8_t* d_desc,
+                            hipStream_t s) {
+    fdfk::DescribeParams p{};
+    p.frames = d_frames;
+    p.frame_stride = frame_stride;
+    p.pts = reinterpret_cast<const uint2*>(d_points);
+    p.offs = d_offsets;
+    p.cap = cap;
+    p.n_frames = n_frames;
+    p.width = width;
+    p.height = height;
+    p.angles = d_angles;
+    p.table = d_table;
+    p.n_bins = n_bins;
+    p.scale = (float)(n_bins / (2 * M_PI));
+    p.desc = d_desc;
+    return fdfk::launch_describe(p, chunks_per_frame(cap, n_frames, width, height, 64, 1024), s);
+}
+
+}  // namespace
+
+int fdf_smooth_device(fdf_ctx* ctx, const uint8_t* d_frames, uint32_t n_frames, uint32_t width,
+                      uint32_t height, uint64_t frame_stride_bytes, uint8_t* d_out,
+                      uint64_t out_frame_stride_bytes, void* stream) {
+    const uint64_t frame_bytes = (uint64_t)width * height;
+    if (!ctx || n_frames > 65535u) return FDF_ERR_ARG;
+    if (frame_bytes == 0 || frame_bytes > fdfk::kOrientMaxPixels) return FDF_ERR_SIZE;
+    if (n_frames == 0) return FDF_OK;
+    if (!d_frames || !d_out) return FDF_ERR_ARG;
+    const uint64_t fs = frame_stride(n_frames, frame_stride_bytes, frame_bytes);
+    const uint64_t os = frame_stride(n_frames, out_frame_stride_bytes, frame_bytes);
+    if (fs < frame_bytes || os < frame_bytes) return FDF_ERR_ARG;
+    DeviceGuard guard(ctx->device);
+    return status_of(smooth_enqueue(d_frames, n_frames, width, height, fs, d_out, os,
+                                    reinterpret_cast<hipStream_t>(stream)));
+}
+
+int fdf_describe_device(fdf_ctx* ctx, const uint8_t* d_frames, uint32_t n_frames, uint32_t width,
+                        uint32_t height, uint64_t frame_stride_bytes, const fdf_point* d_points,
+                        uint64_t cap, const uint64_t* d_frame_offsets, const float* d_angles,
+                        const int8_t* d_table, uint32_t n_bins, uint8_t* d_desc, void* stream) {
+    if (!ctx || !d_frame_offsets || !d_table || n_bins == 0 || n_bins > fdfk::kBriefMaxBins ||
+        n_frames > 65535u)
+        return FDF_ERR_ARG;
+    uint64_t fs = 0;
+    bool todo = false;
+    const int rc = check_point_frames(n_frames, width, height, cap, frame_stride_bytes,
+                                      d_frames && d_points && d_desc, &fs, &todo);
+    if (!todo) return rc;
+    DeviceGuard guard(ctx->device);
+    return status_of(describe_enqueue(d_frames, n_frames, width, height, fs, d_points, cap,
+                                      d_frame_offsets, d_angles, d_table, n_bins, d_desc,
+                                      reinterpret_cast<hipStream_t>(stream)));
+}
+
+int fdf_describe_points(fdf_ctx* ctx, const uint8_t* data, uint32_t width, uint32_t height,
+                        size_t stride_bytes, const fdf_point* points, size_t n_points,
+                        const float* angles, const int8_t* pattern, uint32_t n_bins, int smooth,
+                        uint8_t* out_desc) {
+    if (!ctx || n_bins == 0 || n_bins > fdfk::kBriefMaxBins || (smooth != 0 && smooth != 1))
+        return FDF_ERR_ARG;
+    if (n_points && (!points || !out_desc || !data)) return FDF_ERR_ARG;
+    if (stride_bytes < width) return FDF_ERR_ARG;
+    if (!points_inside(points, n_points, width, height)) return FDF_ERR_ARG;
+    if (n_points == 0) return FDF_OK;
+    const uint64_t frame_bytes = (uint64_t)width * height;
+    if (frame_bytes > fdfk::kOrientMaxPixels) return FDF_ERR_SIZE;
+    int8_t default_pattern[fdfk::kBriefTableBytes];
+    if (!pattern) {
+        fdf_brief_pattern(default_pattern);
+        pattern = default_pattern;
+    }
+    std::vector<int8_t> table((size_t)n_bins * fdfk::kBriefTableBytes);
+    if (fdf_brief_steer(pattern, n_bins, table.data()) != FDF_OK) return FDF_ERR_ARG;
+    Arena a(ctx);
+    const auto d_frame = a.part<uint8_t>(frame_bytes);
+    const auto d_smooth = a.part<uint8_t>(smooth ? frame_bytes : 0);
+    const auto d_pts = a.part<fdf_point>(n_points);
+    const auto d_offs = a.part<uint64_t>(2);
+    const auto d_ang = a.part<float>(angles ? n_points : 0);
+    const auto d_table = a.part<int8_t>(table.size());
+    const auto d_desc = a.part<uint8_t>(n_points * (uint64_t)fdfk::kBriefBytes);
+    if (a.open() != FDF_OK) return FDF_ERR_ALLOC;
+    a.upload_frame(d_frame, data, width, height, stride_bytes);
+    a.upload(d_pts, points);
+    a.upload_one_frame(d_offs, n_points);
+    if (angles) a.upload(d_ang, angles);
+    a.upload(d_table, table.data());
+    if (a.ok() && smooth)
+        a.note(smooth_enqueue(a.at(d_frame), 1, width, height, frame_bytes, a.at(d_smooth),
+                              frame_bytes, ctx->stream));
+    if (a.ok())
+        a.note(describe_enqueue(a.at(smooth ? d_smooth : d_frame), 1, width, height, frame_bytes,
+                                a.at(d_pts), n_points, a.at(d_offs),
+                                angles ? a.at(d_ang) : nullptr, a.at(d_table), n_bins,
+                                a.at(d_desc), ctx->stream));
+    a.download(out_desc, d_desc, d_desc.count);
+    return a.close();
+}
+
+}  // extern "C"

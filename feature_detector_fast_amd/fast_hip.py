@@ -93,6 +93,60 @@ def _as_pixels(img):
     return arr
 
 
+def _host_points(points):
+    """``points`` as a contiguous (K, 2) uint32 array."""
+    pts = np.asarray(points)
+    if pts.ndim != 2 or pts.shape[1] != 2 or pts.dtype.kind not in "ui":
+        raise TypeError("points must be a (K, 2) integer array")
+    if pts.size and (pts.min() < 0 or pts.max() > 0xffffffff):
+        raise ValueError("points must fit u32")
+    return np.ascontiguousarray(pts, dtype=np.uint32)
+
+
+# Argument checks of the device entries (torch tensors).
+
+def _check_points(t, name="points", rows="cap"):
+    if t.dim() != 2 or t.shape[1] != 2 or t.element_size() != 4 or not t.is_contiguous() \
+            or t.is_floating_point():
+        raise ValueError(f"{name} must be a contiguous ({rows}, 2) 32-bit integer tensor")
+
+
+def _check_offsets(torch, t, n, name="offsets", one_dim=True):
+    if t.dtype != torch.int64 or (one_dim and t.dim() != 1) or not t.is_contiguous() or \
+            t.numel() < n:
+        raise ValueError(f"{name} must be a contiguous int64 tensor with F+1 entries")
+
+
+def _check_angles(torch, t, cap):
+    if t.dtype != torch.float32 or t.dim() != 1 or t.numel() < cap or not t.is_contiguous():
+        raise ValueError("angles must be a contiguous float32 tensor with cap entries")
+
+
+def _check_frames(torch, t, name="frames"):
+    """(F, H, W) uint8 with contiguous frames any number of bytes apart."""
+    if t.dim() != 3 or t.dtype != torch.uint8 or (
+            t.numel() and (t.stride(2) != 1 or t.stride(1) != t.shape[2] or
+                           (t.shape[0] > 1 and t.stride(0) < t.shape[1] * t.shape[2]))):
+        raise ValueError(f"{name} must be a (F, H, W) uint8 tensor of contiguous frames")
+
+
+def _frame_args(t):
+    """(pointer, F, width, height, frame stride in bytes) of a _check_frames tensor."""
+    f, h, w = t.shape
+    return t.data_ptr(), f, w, h, t.stride(0) if f > 1 else h * w
+
+
+def _check_one_device(where, tensors):
+    if not all(t.is_cuda for t in tensors) or len({t.device for t in tensors}) != 1:
+        raise ValueError(f"{where} needs CUDA (HIP) tensors on one device")
+
+
+def _device_stream(torch, t, device, stream):
+    """(device index, stream) of a call: ``t``'s device and torch's current stream by default."""
+    return (t.device.index if device is None else device,
+            torch.cuda.current_stream(t.device) if stream is None else stream)
+
+
 def capacity_guess(pixels):
     """First output capacity of the two-call pattern: 1 keypoint per 64 pixels (real images
     have 0.5-1.5 per 100; denser results are fetched with fdf_fetch_last, not recomputed)."""
@@ -176,10 +230,8 @@ def rgb_to_luma(frames, out, stream=None, device=None):
         raise ValueError("out must be a contiguous (F, H, W) uint8 tensor")
     if not frames.is_cuda or not out.is_cuda:
         raise ValueError("rgb_to_luma needs CUDA (HIP) tensors")
-    dev = frames.device.index if device is None else device
+    dev, stream = _device_stream(torch, frames, device, stream)
     ctx = context(dev)
-    if stream is None:
-        stream = torch.cuda.current_stream(frames.device)
     f, h, w = frames.shape[:3]
     lib = _native.load()
     check(lib.fdf_rgb_to_luma_device(ctx.handle, frames.data_ptr(), f, w, h, 3 * w * h,
@@ -253,12 +305,10 @@ def detect_device(frames, config, out, offsets, stream=None, device=None, ctx=No
         raise ValueError("offsets must be int64 with F+1 entries")
     if out.dim() != 2 or out.shape[1] != 2 or out.element_size() != 4 or not out.is_contiguous():
         raise ValueError("out must be a contiguous (cap, 2) 32-bit tensor")
-    dev = frames.device.index if device is None else device
+    dev, stream = _device_stream(torch, frames, device, stream)
     cfg = _to_c_config(config)
     if ctx is None:
         ctx = context(dev)
-    if stream is None:
-        stream = torch.cuda.current_stream(frames.device)
     f, h, w = frames.shape
     rc = _native.load().fdf_detect_device(
         ctx.handle, frames.data_ptr(), f, w, h, h * w, ctypes.byref(cfg), out.data_ptr(),
@@ -383,11 +433,9 @@ def detect_device_rgb(frames, config, out, offsets, stream=None, device=None):
         raise ValueError("offsets must be int64 with F+1 entries")
     if out.dim() != 2 or out.shape[1] != 2 or out.element_size() != 4 or not out.is_contiguous():
         raise ValueError("out must be a contiguous (cap, 2) 32-bit tensor")
-    dev = frames.device.index if device is None else device
+    dev, stream = _device_stream(torch, frames, device, stream)
     cfg = _to_c_config(config)
     ctx = context(dev)
-    if stream is None:
-        stream = torch.cuda.current_stream(frames.device)
     f, h, w = frames.shape[:3]
     rc = _native.load().fdf_detect_device_rgb(
         ctx.handle, frames.data_ptr(), f, w, h, 3 * h * w, ctypes.byref(cfg), out.data_ptr(),
@@ -473,11 +521,9 @@ def score_rings_device(centers, rings, scores, score, threshold=0, consecutive=9
         raise ValueError("scores must be a 16-bit tensor")
     if rings.numel() and rings.data_ptr() % 16 != 0:
         raise ValueError("rings must start on a 16-byte boundary (one 16-byte load per ring)")
-    dev = rings.device.index if device is None else device
+    dev, stream = _device_stream(torch, rings, device, stream)
     cfg = _ring_config(score, threshold, consecutive)
-    if stream is None:
-        stream = torch.cuda.current_stream(rings.device)
-    rc = _native.load().fdf_score_rings_device(
+    rc =_native.load().fdf_score_rings_device(
         context(dev).handle, centers.data_ptr(), rings.data_ptr(), rings.shape[0],
         ctypes.byref(cfg), scores.data_ptr(), ctypes.c_void_p(stream.cuda_stream))
     check(rc, "fdf_score_rings_device")
@@ -537,11 +583,9 @@ def score_device(frames, config, points, offsets, scores, stream=None, device=No
         raise ValueError("scores must be a contiguous 16-bit tensor with cap entries")
     if offsets.dtype != torch.int64 or offsets.numel() < frames.shape[0] + 1:
         raise ValueError("offsets must be int64 with F+1 entries")
-    dev = frames.device.index if device is None else device
+    dev, stream = _device_stream(torch, frames, device, stream)
     cfg = _to_c_config(config)
     ctx = context(dev)
-    if stream is None:
-        stream = torch.cuda.current_stream(frames.device)
     f, h, w = frames.shape
     rc = _native.load().fdf_score_device(
         ctx.handle, frames.data_ptr(), f, w, h, h * w, ctypes.byref(cfg), points.data_ptr(),
@@ -588,32 +632,21 @@ def select_device(points, scores, offsets, shape, cell, k, sel, sel_scores, sel_
 
     cw, ch, k = _cell_k(cell, k)
     h, w = (int(v) for v in shape)
-    for name, t in (("points", points), ("sel", sel)):
-        if t.dim() != 2 or t.shape[1] != 2 or t.element_size() != 4 or not t.is_contiguous() \
-                or t.is_floating_point():
-            raise ValueError(f"{name} must be a contiguous (n, 2) 32-bit integer tensor")
+    _check_points(points, "points", "n")
+    _check_points(sel, "sel", "n")
     for name, t, n in (("scores", scores, points.shape[0]), ("sel_scores", sel_scores, sel.shape[0])):
         if t.dim() != 1 or t.element_size() != 2 or not t.is_contiguous() or \
                 t.is_floating_point() or t.numel() < n:
             raise ValueError(f"{name} must be a contiguous 16-bit integer tensor, one entry per point")
-    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 2 or \
-            not offsets.is_contiguous():
-        raise ValueError("offsets must be a contiguous int64 tensor with F+1 entries")
+    _check_offsets(torch, offsets, 2)
     f = offsets.numel() - 1
-    if sel_offsets.dtype != torch.int64 or sel_offsets.numel() < f + 1 or \
-            not sel_offsets.is_contiguous():
-        raise ValueError("sel_offsets must be a contiguous int64 tensor with F+1 entries")
+    _check_offsets(torch, sel_offsets, f + 1, "sel_offsets", one_dim=False)
     cap = points.shape[0]
     if keep is not None and (keep.dtype != torch.uint8 or keep.numel() < cap or
                              not keep.is_contiguous()):
         raise ValueError("keep must be a contiguous uint8 tensor with cap entries")
-    tensors = [points, scores, offsets, sel, sel_scores, sel_offsets]
-    if keep is not None:
-        tensors.append(keep)
-    if scratch is not None:
-        tensors.append(scratch)
-    if not all(t.is_cuda for t in tensors) or len({t.device for t in tensors}) != 1:
-        raise ValueError("select_device needs CUDA (HIP) tensors on one device")
+    _check_one_device("select_device", [t for t in (points, scores, offsets, sel, sel_scores,
+                                                    sel_offsets, keep, scratch) if t is not None])
     need = select_scratch_bytes(f, (h, w), (cw, ch), cap)
     if scratch is not None and (scratch.dtype != torch.uint8 or not scratch.is_contiguous()):
         raise ValueError("scratch must be a contiguous uint8 tensor")
@@ -715,34 +748,20 @@ def orient_device(frames, points, offsets, angles, radius=15, moments=None, stre
     import torch
 
     r = _radius(radius)
-    if frames.dim() != 3 or frames.dtype != torch.uint8 or \
-            (frames.numel() and (frames.stride(2) != 1 or frames.stride(1) != frames.shape[2]
-                                 or (frames.shape[0] > 1 and
-                                     frames.stride(0) < frames.shape[1] * frames.shape[2]))):
-        raise ValueError("frames must be a (F, H, W) uint8 tensor of contiguous frames")
-    if points.dim() != 2 or points.shape[1] != 2 or points.element_size() != 4 or \
-            not points.is_contiguous() or points.is_floating_point():
-        raise ValueError("points must be a contiguous (cap, 2) 32-bit integer tensor")
+    _check_frames(torch, frames)
+    _check_points(points)
     cap = points.shape[0]
-    if angles.dtype != torch.float32 or angles.dim() != 1 or angles.numel() < cap or \
-            not angles.is_contiguous():
-        raise ValueError("angles must be a contiguous float32 tensor with cap entries")
+    _check_angles(torch, angles, cap)
     if moments is not None and (moments.dtype != torch.int32 or moments.dim() != 2 or
                                 moments.shape[1] != 2 or moments.shape[0] < cap or
                                 not moments.is_contiguous()):
         raise ValueError("moments must be a contiguous (cap, 2) int32 tensor")
-    if offsets.dtype != torch.int64 or offsets.dim() != 1 or not offsets.is_contiguous() or \
-            offsets.numel() < frames.shape[0] + 1:
-        raise ValueError("offsets must be a contiguous int64 tensor with F+1 entries")
-    tensors = [frames, points, offsets, angles] + ([moments] if moments is not None else [])
-    if not all(t.is_cuda for t in tensors) or len({t.device for t in tensors}) != 1:
-        raise ValueError("orient_device needs CUDA (HIP) tensors on one device")
-    dev = frames.device.index if device is None else device
-    if stream is None:
-        stream = torch.cuda.current_stream(frames.device)
-    f, h, w = frames.shape
+    _check_offsets(torch, offsets, frames.shape[0] + 1)
+    _check_one_device("orient_device",
+                      [frames, points, offsets, angles] + ([moments] if moments is not None else []))
+    dev, stream = _device_stream(torch, frames, device, stream)
     rc = _native.load().fdf_orient_device(
-        context(dev).handle, frames.data_ptr(), f, w, h, frames.stride(0) if f > 1 else h * w,
+        context(dev).handle, *_frame_args(frames),
         points.data_ptr(), cap, offsets.data_ptr(), r, angles.data_ptr(),
         moments.data_ptr() if moments is not None else None,
         ctypes.c_void_p(stream.cuda_stream))
@@ -755,12 +774,7 @@ def keypoint_angles(img, points, radius=15, device=0, moments=False):
     (K, 2) int32 (m10, m01).  Points outside the image are an error."""
     r = _radius(radius)
     arr = _as_pixels(img)
-    pts = np.asarray(points)
-    if pts.ndim != 2 or pts.shape[1] != 2 or pts.dtype.kind not in "ui":
-        raise TypeError("points must be a (K, 2) integer array")
-    if pts.size and (pts.min() < 0 or pts.max() > 0xffffffff):
-        raise ValueError("points must fit u32")
-    pts = np.ascontiguousarray(pts, dtype=np.uint32)
+    pts = _host_points(points)
     h, w = arr.shape
     n = pts.shape[0]
     angles = np.zeros(n, dtype=np.float32)
@@ -815,13 +829,6 @@ def brief_steer(pattern, n_bins):
     return table
 
 
-def _is_frames(torch, t):
-    """(F, H, W) uint8 with contiguous frames any number of bytes apart."""
-    return t.dim() == 3 and t.dtype == torch.uint8 and not (
-        t.numel() and (t.stride(2) != 1 or t.stride(1) != t.shape[2] or
-                       (t.shape[0] > 1 and t.stride(0) < t.shape[1] * t.shape[2])))
-
-
 def smooth_device(frames, out, stream=None, device=None):
     """5 x 5 box smoothing on the device (fdf_smooth_device): ``out`` = (sum of the 5 x 5
     neighbourhood at clamped coordinates + 12) // 25.  ``frames`` and ``out`` are (F, H, W)
@@ -830,27 +837,24 @@ def smooth_device(frames, out, stream=None, device=None):
     Asynchronous on ``stream`` (default: torch's current stream)."""
     import torch
 
-    for name, t in (("frames", frames), ("out", out)):
-        if not _is_frames(torch, t):
-            raise ValueError(f"{name} must be a (F, H, W) uint8 tensor of contiguous frames")
+    _check_frames(torch, frames)
+    _check_frames(torch, out, "out")
     if frames.shape != out.shape:
         raise ValueError("frames and out must have the same shape")
     f, h, w = frames.shape
     if f > 65535 or h < 1 or w < 1 or h * w > 0x7fffff00:
         raise ValueError("at most 65535 frames of 1 <= width * height <= 2^31 - 256 pixels")
-    if not (frames.is_cuda and out.is_cuda) or frames.device != out.device:
-        raise ValueError("smooth_device needs CUDA (HIP) tensors on one device")
+    _check_one_device("smooth_device", [frames, out])
     if f:
         span = lambda t: (t.data_ptr(), t.data_ptr() + (f - 1) * t.stride(0) + h * w)
         (a0, a1), (b0, b1) = span(frames), span(out)
         if a0 < b1 and b0 < a1:
             raise ValueError("frames and out must not overlap")
-    dev = frames.device.index if device is None else device
-    if stream is None:
-        stream = torch.cuda.current_stream(frames.device)
+    dev, stream = _device_stream(torch, frames, device, stream)
+    out_ptr, _, _, _, out_stride = _frame_args(out)
     rc = _native.load().fdf_smooth_device(
-        context(dev).handle, frames.data_ptr(), f, w, h, frames.stride(0) if f > 1 else h * w,
-        out.data_ptr(), out.stride(0) if f > 1 else h * w, ctypes.c_void_p(stream.cuda_stream))
+        context(dev).handle, *_frame_args(frames), out_ptr, out_stride,
+        ctypes.c_void_p(stream.cuda_stream))
     check(rc, "fdf_smooth_device")
 
 
@@ -867,32 +871,22 @@ def describe_device(frames, points, offsets, desc, table, n_bins, angles=None, s
     import torch
 
     n = _n_bins(n_bins)
-    if not _is_frames(torch, frames):
-        raise ValueError("frames must be a (F, H, W) uint8 tensor of contiguous frames")
-    if points.dim() != 2 or points.shape[1] != 2 or points.element_size() != 4 or \
-            not points.is_contiguous() or points.is_floating_point():
-        raise ValueError("points must be a contiguous (cap, 2) 32-bit integer tensor")
+    _check_frames(torch, frames)
+    _check_points(points)
     cap = points.shape[0]
     if desc.dtype != torch.uint8 or desc.dim() != 2 or desc.shape[1] != 32 or \
             desc.shape[0] < cap or not desc.is_contiguous():
         raise ValueError("desc must be a contiguous (cap, 32) uint8 tensor")
     if table.dtype != torch.int8 or not table.is_contiguous() or table.numel() != n * 1024:
         raise ValueError("table must be a contiguous int8 tensor of n_bins * 256 * 4 entries")
-    if angles is not None and (angles.dtype != torch.float32 or angles.dim() != 1 or
-                               angles.numel() < cap or not angles.is_contiguous()):
-        raise ValueError("angles must be a contiguous float32 tensor with cap entries")
-    if offsets.dtype != torch.int64 or offsets.dim() != 1 or not offsets.is_contiguous() or \
-            offsets.numel() < frames.shape[0] + 1:
-        raise ValueError("offsets must be a contiguous int64 tensor with F+1 entries")
-    tensors = [frames, points, offsets, desc, table] + ([angles] if angles is not None else [])
-    if not all(t.is_cuda for t in tensors) or len({t.device for t in tensors}) != 1:
-        raise ValueError("describe_device needs CUDA (HIP) tensors on one device")
-    dev = frames.device.index if device is None else device
-    if stream is None:
-        stream = torch.cuda.current_stream(frames.device)
-    f, h, w = frames.shape
+    if angles is not None:
+        _check_angles(torch, angles, cap)
+    _check_offsets(torch, offsets, frames.shape[0] + 1)
+    _check_one_device("describe_device", [frames, points, offsets, desc, table] +
+                      ([angles] if angles is not None else []))
+    dev, stream = _device_stream(torch, frames, device, stream)
     rc = _native.load().fdf_describe_device(
-        context(dev).handle, frames.data_ptr(), f, w, h, frames.stride(0) if f > 1 else h * w,
+        context(dev).handle, *_frame_args(frames),
         points.data_ptr(), cap, offsets.data_ptr(),
         angles.data_ptr() if angles is not None else None, table.data_ptr(), n,
         desc.data_ptr(), ctypes.c_void_p(stream.cuda_stream))
@@ -908,12 +902,7 @@ def keypoint_descriptors(img, points, angles=None, pattern=None, n_bins=30, smoo
     Points outside the image are an error."""
     n = _n_bins(n_bins)
     arr = _as_pixels(img)
-    pts = np.asarray(points)
-    if pts.ndim != 2 or pts.shape[1] != 2 or pts.dtype.kind not in "ui":
-        raise TypeError("points must be a (K, 2) integer array")
-    if pts.size and (pts.min() < 0 or pts.max() > 0xffffffff):
-        raise ValueError("points must fit u32")
-    pts = np.ascontiguousarray(pts, dtype=np.uint32)
+    pts = _host_points(points)
     k = pts.shape[0]
     if angles is not None:
         ang = np.asarray(angles)

@@ -2,6 +2,8 @@
 (host only) and the argument checks of the Python wrappers (which run before any device
 call)."""
 import ctypes
+import os
+import subprocess
 
 import numpy as np
 import pytest
@@ -98,3 +100,13 @@ def test_orient_device_rejects_bad_arguments():
                 dict()):                          # the same without moments
         with pytest.raises(ValueError):
             call(**bad)
+
+
+def test_wg_share_binary():
+    """The kernels' split of a frame's points over workgroups (fdfk::wg_share), checked on
+    the host by tests/cpp/test_wg_share: contiguous, disjoint, covering, on pass boundaries,
+    and equal to the arithmetic written out."""
+    exe = os.path.join(os.path.dirname(os.path.abspath(__file__)), "cpp", "test_wg_share")
+    res = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert res.returncode == 0, res.stdout + res.stderr
+    assert "630 cases, 0 failures" in res.stdout
