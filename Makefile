@@ -3,7 +3,8 @@
 #   liboracle.so     scalar C restatement of the reference semantics (test infrastructure)
 #   libfast_avx2.so  C++ AVX2 port of the reference's fast_simd path (CPU baseline only)
 #   tests/cpp/test_cpp_*   smoke binaries of the C++ API (include/fdf.hpp): detection,
-#                          fdf::select_best, fdf::keypoint_angles, fdf::keypoint_descriptors
+#                          fdf::select_best, fdf::keypoint_angles, fdf::keypoint_descriptors,
+#                          fdf::match_descriptors
 #   tests/cpp/test_wg_share  host-only check of the kernels' work split (fdf_common.h)
 HIPCC ?= /opt/rocm/bin/hipcc
 CC ?= gcc
@@ -15,9 +16,9 @@ CSRC := $(PKG)/csrc
 LIBFDF := $(PKG)/libfdf.so
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Iinclude $(EXTRA_HIPFLAGS)
 OBJS := $(addprefix $(CSRC)/fdf_,$(addsuffix .o,kernels sweep sweep_latency sweep_rgb select \
-	orient describe api stages pipeline))
+	orient describe match api stages pipeline))
 HEADERS := $(wildcard $(CSRC)/*.h) include/fdf.h
-CPP_TESTS := $(addprefix tests/cpp/test_cpp_,api select orient describe)
+CPP_TESTS := $(addprefix tests/cpp/test_cpp_,api select orient describe match)
 
 all: $(LIBFDF) oracle/liboracle.so oracle/libfast_avx2.so $(CPP_TESTS) tests/cpp/test_wg_share
 

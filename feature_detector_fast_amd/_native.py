@@ -43,7 +43,8 @@ EXPORTED_SYMBOLS = (
     "fdf_ctx_recoveries", "fdf_ctx_test_skew_tickets", "fdf_select_scratch_bytes",
     "fdf_select_device", "fdf_select_points", "fdf_orient_disc", "fdf_orient_device",
     "fdf_orient_points", "fdf_brief_pattern", "fdf_brief_steer", "fdf_smooth_device",
-    "fdf_describe_device", "fdf_describe_points",
+    "fdf_describe_device", "fdf_describe_points", "fdf_match_device",
+    "fdf_match_filter_device", "fdf_match_points",
 )
 
 
@@ -53,6 +54,16 @@ class FdfConfig(ctypes.Structure):
 
 class FdfPoint(ctypes.Structure):
     _fields_ = [("x", ctypes.c_uint32), ("y", ctypes.c_uint32)]
+
+
+class FdfMatch(ctypes.Structure):
+    """include/fdf.h fdf_match: 8 bytes."""
+    _fields_ = [("index", ctypes.c_uint32), ("distance", ctypes.c_uint16),
+                ("second", ctypes.c_uint16)]
+
+
+FDF_MATCH_NONE = 0xFFFFFFFF
+FDF_MATCH_NO_DISTANCE = 0xFFFF
 
 
 class FdfError(RuntimeError):
@@ -208,6 +219,12 @@ def load():
     lib.fdf_describe_points.restype = ctypes.c_int
     lib.fdf_describe_points.argtypes = [vp, vp, u32, u32, sz, vp, sz, vp, vp, u32, ctypes.c_int,
                                         vp]
+    lib.fdf_match_device.restype = ctypes.c_int
+    lib.fdf_match_device.argtypes = [vp, u32, vp, vp, u64, vp, vp, vp, u64, vp, u32, u32, vp, vp]
+    lib.fdf_match_filter_device.restype = ctypes.c_int
+    lib.fdf_match_filter_device.argtypes = [vp, u32, vp, u64, vp, vp, u64, u32, u32, u32, vp, vp]
+    lib.fdf_match_points.restype = ctypes.c_int
+    lib.fdf_match_points.argtypes = [vp, vp, vp, sz, vp, vp, sz, u32, u32, vp]
     del u8p
     _lib = lib
     return lib

@@ -1,5 +1,5 @@
 // fdf_kernels.h -- shared between the HIP kernels (fdf_sweep.hip, fdf_kernels.hip,
-// fdf_select.hip, fdf_orient.hip, fdf_describe.hip) and the C-ABI host layer (fdf_api.cpp,
+// fdf_select.hip, fdf_orient.hip, fdf_describe.hip, fdf_match.hip) and the C-ABI host layer (fdf_api.cpp,
 // fdf_stages.cpp): geometry constants, LDS layout and launch parameters.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -345,5 +345,37 @@ struct SmoothParams {
     uint32_t strip_rows, strips; // rows a thread walks; strips = ceil(height / strip_rows)
 };
 hipError_t launch_smooth(const SmoothParams& p, hipStream_t stream);
+
+// Brute-force Hamming matching of the 256-bit descriptors (fdf_match.hip; fdf_match_device,
+// fdf_match_filter_device).
+constexpr int kMatchThreads = 256;                    // queries of a workgroup pass
+constexpr uint32_t kMatchTile = 256;                  // train descriptors of an LDS tile
+constexpr uint32_t kMatchNone = 0xffffffffu;          // FDF_MATCH_NONE
+constexpr uint32_t kMatchNoDistance = 0xffffu;        // FDF_MATCH_NO_DISTANCE
+constexpr uint64_t kMatchMaxCap = 0xfffffffeull;      // indices are u32 and kMatchNone is none
+struct MatchParams {
+    const uint8_t* q_desc;       // `q_cap` * kBriefBytes, 4-byte aligned
+    const uint2* q_pts;          // `q_cap` points, or NULL with t_pts: no window
+    const uint64_t* q_offs;      // n_frames + 1 entries
+    uint64_t q_cap;
+    const uint8_t* t_desc;       // `t_cap` * kBriefBytes, 4-byte aligned
+    const uint2* t_pts;          // `t_cap` points, each frame's y non-decreasing
+    const uint64_t* t_offs;      // n_frames + 1 entries
+    uint64_t t_cap;
+    uint32_t n_frames, max_dx, max_dy;
+    uint2* matches;              // `q_cap` fdf_match: .x = index, .y = distance | second << 16
+};
+// one kernel on `stream`: `chunks` workgroups per frame share the frame's queries
+hipError_t launch_match(const MatchParams& p, uint32_t chunks, hipStream_t stream);
+struct MatchFilterParams {
+    const uint2* matches;        // `q_cap` fdf_match
+    const uint64_t* q_offs;      // n_frames + 1 entries
+    uint64_t q_cap;
+    const uint2* reverse;        // `t_cap` fdf_match, or NULL: no cross-check
+    uint64_t t_cap;
+    uint32_t n_frames, max_distance, ratio_num, ratio_den;
+    uint8_t* keep;               // `q_cap` flags
+};
+hipError_t launch_match_filter(const MatchFilterParams& p, hipStream_t stream);
 
 }  // namespace fdfk

@@ -1,6 +1,6 @@
 // fdf_stages.cpp -- the C ABI of the stages behind the detector (extensions: the reference
-// returns points only): best-K selection, orientation, steered BRIEF descriptors and box
-// smoothing.  Each has an asynchronous _device entry on the caller's stream and memory and a
+// returns points only): best-K selection, orientation, steered BRIEF descriptors, box
+// smoothing and descriptor matching.  Each has an asynchronous _device entry on the caller's stream and memory and a
 // host convenience _points entry.  Of a context they use the device, the mutex and the
 // stream only: its workspace and retained result (fdf_fetch_last) are not touched.
 #include <algorithm>
@@ -547,6 +547,118 @@ int fdf_describe_points(fdf_ctx* ctx, const uint8_t* data, uint32_t width, uint3
                                 angles ? a.at(d_ang) : nullptr, a.at(d_table), n_bins,
                                 a.at(d_desc), ctx->stream));
     a.download(out_desc, d_desc, d_desc.count);
+    return a.close();
+}
+
+// ---- brute-force Hamming matching (fdf_match.hip) ------------------------------------------
+namespace {
+
+static_assert(sizeof(fdf_match) == 8 && sizeof(fdf_match) == sizeof(uint2), "fdf_match is 8 bytes");
+static_assert(FDF_MATCH_NONE == fdfk::kMatchNone && FDF_MATCH_NO_DISTANCE == fdfk::kMatchNoDistance,
+              "the kernels' constants are the header's");
+
+// The launch of fdf_match_device / fdf_match_points (arguments already validated).
+hipError_t match_enqueue(uint32_t n_frames, const uint8_t* d_q_desc, const fdf_point* d_q_points,
+                         uint64_t q_cap, const uint64_t* d_q_offsets, const uint8_t* d_t_desc,
+                         const fdf_point* d_t_points, uint64_t t_cap, const uint64_t* d_t_offsets,
+                         uint32_t max_dx, uint32_t max_dy, fdf_match* d_matches, hipStream_t s) {
+    fdfk::MatchParams p{};
+    p.q_desc = d_q_desc;
+    p.q_pts = reinterpret_cast<const uint2*>(d_q_points);
+    p.q_offs = d_q_offsets;
+    p.q_cap = q_cap;
+    p.t_desc = d_t_desc;
+    p.t_pts = reinterpret_cast<const uint2*>(d_t_points);
+    p.t_offs = d_t_offsets;
+    p.t_cap = t_cap;
+    p.n_frames = n_frames;
+    p.max_dx = max_dx;
+    p.max_dy = max_dy;
+    p.matches = reinterpret_cast<uint2*>(d_matches);
+    // a workgroup per 256 queries of a frame at the mean frame size, 1024 at most
+    const uint32_t chunks =
+        (uint32_t)std::min<uint64_t>(1024, q_cap / n_frames / fdfk::kMatchThreads + 1);
+    return fdfk::launch_match(p, chunks, s);
+}
+
+}  // namespace
+
+int fdf_match_device(fdf_ctx* ctx, uint32_t n_frames, const uint8_t* d_q_desc,
+                     const fdf_point* d_q_points, uint64_t q_cap, const uint64_t* d_q_offsets,
+                     const uint8_t* d_t_desc, const fdf_point* d_t_points, uint64_t t_cap,
+                     const uint64_t* d_t_offsets, uint32_t max_dx, uint32_t max_dy,
+                     fdf_match* d_matches, void* stream) {
+    if (!ctx || !d_q_offsets || !d_t_offsets || n_frames > 65535u ||
+        q_cap > fdfk::kMatchMaxCap || t_cap > fdfk::kMatchMaxCap ||
+        (d_q_points == nullptr) != (d_t_points == nullptr))
+        return FDF_ERR_ARG;
+    if (n_frames == 0 || q_cap == 0) return FDF_OK;
+    if (!d_q_desc || !d_matches || (t_cap && !d_t_desc) || ((uintptr_t)d_q_desc & 3u) != 0 ||
+        ((uintptr_t)d_t_desc & 3u) != 0 || ((uintptr_t)d_matches & 7u) != 0)
+        return FDF_ERR_ARG;
+    DeviceGuard guard(ctx->device);
+    return status_of(match_enqueue(n_frames, d_q_desc, d_q_points, q_cap, d_q_offsets, d_t_desc,
+                                   d_t_points, t_cap, d_t_offsets, max_dx, max_dy, d_matches,
+                                   reinterpret_cast<hipStream_t>(stream)));
+}
+
+int fdf_match_filter_device(fdf_ctx* ctx, uint32_t n_frames, const fdf_match* d_matches,
+                            uint64_t q_cap, const uint64_t* d_q_offsets,
+                            const fdf_match* d_reverse, uint64_t t_cap, uint32_t max_distance,
+                            uint32_t ratio_num, uint32_t ratio_den, uint8_t* d_keep,
+                            void* stream) {
+    if (!ctx || !d_q_offsets || n_frames > 65535u || q_cap > fdfk::kMatchMaxCap ||
+        t_cap > fdfk::kMatchMaxCap || ratio_num > 65535u || ratio_den > 65535u)
+        return FDF_ERR_ARG;
+    if (n_frames == 0 || q_cap == 0) return FDF_OK;
+    if (!d_matches || !d_keep || ((uintptr_t)d_matches & 7u) != 0 ||
+        ((uintptr_t)d_reverse & 7u) != 0)
+        return FDF_ERR_ARG;
+    fdfk::MatchFilterParams p{};
+    p.matches = reinterpret_cast<const uint2*>(d_matches);
+    p.q_offs = d_q_offsets;
+    p.q_cap = q_cap;
+    p.reverse = reinterpret_cast<const uint2*>(d_reverse);
+    p.t_cap = t_cap;
+    p.n_frames = n_frames;
+    p.max_distance = max_distance;
+    p.ratio_num = ratio_num;
+    p.ratio_den = ratio_den;
+    p.keep = d_keep;
+    DeviceGuard guard(ctx->device);
+    return status_of(fdfk::launch_match_filter(p, reinterpret_cast<hipStream_t>(stream)));
+}
+
+int fdf_match_points(fdf_ctx* ctx, const uint8_t* q_desc, const fdf_point* q_points, size_t n_q,
+                     const uint8_t* t_desc, const fdf_point* t_points, size_t n_t,
+                     uint32_t max_dx, uint32_t max_dy, fdf_match* out) {
+    if (!ctx || (q_points == nullptr) != (t_points == nullptr)) return FDF_ERR_ARG;
+    if (n_q > fdfk::kMatchMaxCap || n_t > fdfk::kMatchMaxCap) return FDF_ERR_ARG;
+    if (n_q && (!q_desc || !out)) return FDF_ERR_ARG;
+    if (n_t && !t_desc) return FDF_ERR_ARG;
+    if (n_q == 0) return FDF_OK;
+    const bool window = q_points != nullptr;
+    const uint64_t t_offs[2] = {0, n_t};                  // an asynchronous copy's source
+    Arena a(ctx);
+    const auto d_q = a.part<uint8_t>(n_q * (uint64_t)fdfk::kBriefBytes);
+    const auto d_t = a.part<uint8_t>(n_t * (uint64_t)fdfk::kBriefBytes);
+    const auto d_qp = a.part<fdf_point>(window ? n_q : 0);
+    const auto d_tp = a.part<fdf_point>(window ? n_t : 0);
+    const auto d_qo = a.part<uint64_t>(2);
+    const auto d_to = a.part<uint64_t>(2);
+    const auto d_out = a.part<fdf_match>(n_q);
+    if (a.open() != FDF_OK) return FDF_ERR_ALLOC;
+    a.upload(d_q, q_desc);
+    if (n_t) a.upload(d_t, t_desc);
+    if (window) a.upload(d_qp, q_points);
+    if (window && n_t) a.upload(d_tp, t_points);
+    a.upload_one_frame(d_qo, n_q);
+    a.upload(d_to, t_offs);
+    if (a.ok())
+        a.note(match_enqueue(1, a.at(d_q), window ? a.at(d_qp) : nullptr, n_q, a.at(d_qo),
+                             a.at(d_t), window ? a.at(d_tp) : nullptr, n_t, a.at(d_to), max_dx,
+                             max_dy, a.at(d_out), ctx->stream));
+    a.download(out, d_out, n_q);
     return a.close();
 }
 

@@ -934,6 +934,224 @@ def detect_described_array(img, config, radius=15, n_bins=30, device=0):
     return pts, angles, keypoint_descriptors(arr, pts, angles, n_bins=n, device=device)
 
 
+# include/fdf.h fdf_match as a numpy record; the (n, 2) 32-bit layout of the device wrappers
+# holds the same 8 bytes: column 0 the index, column 1 distance | second << 16.
+MATCH_DTYPE = np.dtype([("index", "<u4"), ("distance", "<u2"), ("second", "<u2")])
+MATCH_NONE = _native.FDF_MATCH_NONE
+MATCH_NO_DISTANCE = _native.FDF_MATCH_NO_DISTANCE
+_MATCH_MAX_CAP = 0xFFFFFFFE
+
+
+def _check_desc(torch, t, name):
+    if t.dtype != torch.uint8 or t.dim() != 2 or t.shape[1] != 32 or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous (cap, 32) uint8 tensor")
+    if t.shape[0] > _MATCH_MAX_CAP:
+        raise ValueError(f"{name} must have fewer than 2^32 - 1 rows")
+    if t.data_ptr() % 4:
+        raise ValueError(f"{name} must be 4-byte aligned")
+
+
+def _check_matches(t, name, rows, cap=0):
+    _check_points(t, name, rows)
+    if t.shape[0] < cap or t.shape[0] > _MATCH_MAX_CAP:
+        raise ValueError(f"{name} must have at least {rows} and fewer than 2^32 - 1 rows")
+    if t.data_ptr() % 8:
+        raise ValueError(f"{name} must be 8-byte aligned")
+
+
+def _match_frames(torch, q_offsets, t_offsets=None):
+    """n_frames of a match call: the offsets' length less one."""
+    _check_offsets(torch, q_offsets, 1, "q_offsets")
+    n = q_offsets.numel() - 1
+    if t_offsets is not None:
+        _check_offsets(torch, t_offsets, 1, "t_offsets")
+        if t_offsets.numel() != q_offsets.numel():
+            raise ValueError("q_offsets and t_offsets must have the same length")
+    if n > 65535:
+        raise ValueError("at most 65535 frames")
+    return n
+
+
+def _window(window, have_points):
+    """(max_dx, max_dy) of a match call; (0, 0) without points."""
+    if not have_points:
+        if window is not None:
+            raise ValueError("a window needs q_points and t_points")
+        return 0, 0
+    if window is None:
+        raise ValueError("q_points and t_points need a window (max_dx, max_dy)")
+    try:
+        dx, dy = (int(v) for v in window)
+    except (TypeError, ValueError):
+        raise TypeError("window must be a pair (max_dx, max_dy) of integers") from None
+    if not (0 <= dx <= 0xffffffff and 0 <= dy <= 0xffffffff):
+        raise ValueError("window terms must fit u32")
+    return dx, dy
+
+
+def _ratio(ratio):
+    """(num, den) of the ratio test; (0, 0) when it is off."""
+    if ratio is None:
+        return 0, 0
+    try:
+        num, den = (int(v) for v in ratio)
+    except (TypeError, ValueError):
+        raise TypeError("ratio must be a pair (num, den) of integers") from None
+    if not (0 <= num <= 65535 and 0 <= den <= 65535):
+        raise ValueError("ratio terms must be in 0..65535")
+    return num, den
+
+
+def _max_distance(max_distance):
+    d = int(max_distance)
+    if not 0 <= d <= 0xffffffff:
+        raise ValueError("max_distance must fit u32")
+    return d
+
+
+def match_device(q_desc, q_offsets, t_desc, t_offsets, matches, q_points=None, t_points=None,
+                 window=None, stream=None, device=None):
+    """Brute-force Hamming matching of describe_device's output, on the device
+    (fdf_match_device): frame f of the query set (``q_desc`` (q_cap, 32) uint8, ``q_offsets``
+    (F+1,) int64) against frame f of the train set (``t_desc``, ``t_offsets``, the same
+    length).  The two sets may be one tensor: ``offs[:-1]`` / ``offs[1:]`` over the same
+    ``desc`` match every frame against the next.  ``matches`` (q_cap, 2) 32-bit integers gets
+    per query the global train index of the nearest descriptor (ties: the lowest index; -1 =
+    none) in column 0 and distance | second << 16 in column 1 (unpack_matches).  With
+    ``q_points`` / ``t_points`` ((cap, 2), as detect_device filled them; each train frame's y
+    non-decreasing) and ``window`` = (max_dx, max_dy) only train points within the window
+    are candidates.  Asynchronous on ``stream`` (default: torch's current stream)."""
+    import torch
+
+    _check_desc(torch, q_desc, "q_desc")
+    _check_desc(torch, t_desc, "t_desc")
+    q_cap, t_cap = q_desc.shape[0], t_desc.shape[0]
+    _check_matches(matches, "matches", "q_cap", q_cap)
+    n = _match_frames(torch, q_offsets, t_offsets)
+    if (q_points is None) != (t_points is None):
+        raise ValueError("q_points and t_points go together")
+    have_points = q_points is not None
+    if have_points:
+        _check_points(q_points, "q_points", "q_cap")
+        _check_points(t_points, "t_points", "t_cap")
+        if q_points.shape[0] < q_cap or t_points.shape[0] < t_cap:
+            raise ValueError("q_points / t_points must have a row per descriptor")
+    dx, dy = _window(window, have_points)
+    _check_one_device("match_device", [q_desc, q_offsets, t_desc, t_offsets, matches] +
+                      ([q_points, t_points] if have_points else []))
+    dev, stream = _device_stream(torch, q_desc, device, stream)
+    rc = _native.load().fdf_match_device(
+        context(dev).handle, n, q_desc.data_ptr(),
+        q_points.data_ptr() if have_points else None, q_cap, q_offsets.data_ptr(),
+        t_desc.data_ptr(), t_points.data_ptr() if have_points else None, t_cap,
+        t_offsets.data_ptr(), dx, dy, matches.data_ptr(), ctypes.c_void_p(stream.cuda_stream))
+    check(rc, "fdf_match_device")
+
+
+def match_filter_device(matches, q_offsets, keep, reverse=None, max_distance=256, ratio=None,
+                        stream=None, device=None):
+    """The usual tests on match_device's output, on the device (fdf_match_filter_device):
+    ``keep`` (q_cap,) uint8 gets 1 for every query of ``q_offsets``' frames whose match exists,
+    has distance <= ``max_distance`` (256 and above: off), passes the ratio test distance * den
+    < second * num for ``ratio`` = (num, den) (None: off; Lowe's 0.75 is (3, 4)) and, with
+    ``reverse`` (the (t_cap, 2) matches of the swapped sets), is its match's match; 0 for the
+    others.  Asynchronous on ``stream`` (default: torch's current stream)."""
+    import torch
+
+    _check_matches(matches, "matches", "q_cap")
+    q_cap = matches.shape[0]
+    if keep.dtype != torch.uint8 or keep.dim() != 1 or keep.numel() < q_cap or \
+            not keep.is_contiguous():
+        raise ValueError("keep must be a contiguous uint8 tensor with q_cap entries")
+    if reverse is not None:
+        _check_matches(reverse, "reverse", "t_cap")
+    n = _match_frames(torch, q_offsets)
+    num, den = _ratio(ratio)
+    dist = _max_distance(max_distance)
+    _check_one_device("match_filter_device",
+                      [matches, q_offsets, keep] + ([reverse] if reverse is not None else []))
+    dev, stream = _device_stream(torch, matches, device, stream)
+    rc = _native.load().fdf_match_filter_device(
+        context(dev).handle, n, matches.data_ptr(), q_cap, q_offsets.data_ptr(),
+        reverse.data_ptr() if reverse is not None else None,
+        reverse.shape[0] if reverse is not None else 0, dist, num, den, keep.data_ptr(),
+        ctypes.c_void_p(stream.cuda_stream))
+    check(rc, "fdf_match_filter_device")
+
+
+def unpack_matches(array):
+    """(index, distance, second) of a matches array in either layout, the (n,) records of
+    MATCH_DTYPE or the (n, 2) 32-bit integers of match_device: index as int64 with -1 for no
+    match, distance and second as uint16 (0xFFFF: none)."""
+    a = np.asarray(array)
+    if a.dtype == MATCH_DTYPE and a.ndim == 1:
+        rec = a
+    elif a.ndim == 2 and a.shape[1] == 2 and a.dtype.kind in "ui" and a.dtype.itemsize == 4:
+        rec = np.ascontiguousarray(a).view(MATCH_DTYPE).reshape(-1)
+    else:
+        raise TypeError("expected (n,) match records or an (n, 2) 32-bit integer array")
+    index = rec["index"].astype(np.int64)
+    index[rec["index"] == MATCH_NONE] = -1
+    return index, rec["distance"].copy(), rec["second"].copy()
+
+
+def _host_desc(desc, name):
+    d = np.asarray(desc)
+    if d.dtype != np.uint8 or d.ndim != 2 or d.shape[1] != 32:
+        raise TypeError(f"{name} must be a (K, 32) uint8 array")
+    return np.ascontiguousarray(d)
+
+
+def _match_points(q, t, qp, tp, dx, dy, device):
+    out = np.zeros(len(q), dtype=MATCH_DTYPE)
+    rc = _native.load().fdf_match_points(
+        context(device).handle, q.ctypes.data if len(q) else None,
+        qp.ctypes.data if qp is not None else None, len(q), t.ctypes.data if len(t) else None,
+        tp.ctypes.data if tp is not None else None, len(t), dx, dy,
+        out.ctypes.data if len(q) else None)
+    check(rc, "fdf_match_points")
+    return out
+
+
+def match_descriptors(q_desc, t_desc, q_points=None, t_points=None, window=None,
+                      cross_check=False, ratio=None, max_distance=256, device=0):
+    """Nearest and second nearest train descriptor of every query descriptor
+    (fdf_match_points): (n_q,) records of MATCH_DTYPE (index = MATCH_NONE: no candidate).
+    ``q_desc`` (n_q, 32) and ``t_desc`` (n_t, 32) uint8; with ``q_points`` / ``t_points``
+    ((n, 2), the train points' y non-decreasing) and ``window`` = (max_dx, max_dy) only train
+    points within the window are candidates.  When a filter is asked for -- ``cross_check``,
+    ``ratio`` = (num, den) or ``max_distance`` below 256 -- also returns the (n_q,) bool mask
+    of the matches that pass (the rule of match_filter_device, applied on the host)."""
+    q = _host_desc(q_desc, "q_desc")
+    t = _host_desc(t_desc, "t_desc")
+    if (q_points is None) != (t_points is None):
+        raise ValueError("q_points and t_points go together")
+    have_points = q_points is not None
+    qp = tp = None
+    if have_points:
+        qp, tp = _host_points(q_points), _host_points(t_points)
+        if len(qp) != len(q) or len(tp) != len(t):
+            raise ValueError("one point per descriptor")
+    dx, dy = _window(window, have_points)
+    num, den = _ratio(ratio)
+    dist = _max_distance(max_distance)
+    fwd = _match_points(q, t, qp, tp, dx, dy, device)
+    if not (cross_check or ratio is not None or dist < 256):
+        return fwd
+    d, s = fwd["distance"].astype(np.uint32), fwd["second"].astype(np.uint32)
+    keep = fwd["index"] != MATCH_NONE
+    if dist < 256:
+        keep &= d <= dist
+    if den:
+        keep &= (s == MATCH_NO_DISTANCE) | (d * np.uint32(den) < s * np.uint32(num))
+    if cross_check:
+        rev = _match_points(t, q, tp, qp, dx, dy, device)
+        at = np.minimum(fwd["index"], max(len(t) - 1, 0))
+        back = rev["index"][at] if len(t) else np.full(len(q), MATCH_NONE, np.uint32)
+        keep &= (fwd["index"] < len(t)) & (back == np.arange(len(q), dtype=np.uint32))
+    return fwd, keep
+
+
 __all__ = ["NORTH", "EAST", "SOUTH", "WEST", "circle", "calculate_offsets", "context",
            "shard_contexts", "capacity_guess", "Lanes",
            "detect_array", "detector", "detector_batch", "detect_device", "keypoint_scores",
@@ -942,6 +1160,8 @@ __all__ = ["NORTH", "EAST", "SOUTH", "WEST", "circle", "calculate_offsets", "con
            "orient_disc", "orient_device", "keypoint_angles", "detect_oriented_array",
            "brief_pattern", "brief_steer", "smooth_device", "describe_device",
            "keypoint_descriptors", "detect_described_array",
+           "MATCH_DTYPE", "MATCH_NONE", "MATCH_NO_DISTANCE", "match_device",
+           "match_filter_device", "unpack_matches", "match_descriptors",
            "detect_rgb_array", "detector_rgb", "rgb_to_luma", "detect_device_rgb",
            "score_rings", "score_rings_device", "keypoint_score_max_threshold",
            "keypoint_score_sum_abs_difference", "NonMaximalSuppression"]

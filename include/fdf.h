@@ -34,7 +34,8 @@ extern "C" {
 /* 6 still: fdf_select_scratch_bytes, fdf_select_device and fdf_select_points were added
  * without changing any existing function, which is backward compatible; so were
  * fdf_orient_disc, fdf_orient_device and fdf_orient_points, and fdf_brief_pattern,
- * fdf_brief_steer, fdf_smooth_device, fdf_describe_device and fdf_describe_points. */
+ * fdf_brief_steer, fdf_smooth_device, fdf_describe_device and fdf_describe_points, and
+ * fdf_match_device, fdf_match_filter_device and fdf_match_points. */
 #define FDF_ABI_VERSION 6
 
 /* Status codes.  Shapes the reference maps to an empty Vec return FDF_OK with 0 points. */
@@ -512,6 +513,82 @@ int fdf_describe_points(fdf_ctx* ctx, const uint8_t* data, uint32_t width, uint3
                         size_t stride_bytes, const fdf_point* points, size_t n_points,
                         const float* angles, const int8_t* pattern, uint32_t n_bins, int smooth,
                         uint8_t* out_desc);
+
+/*
+ * Brute-force Hamming matching of the descriptors (extension: the reference returns points
+ * only; the step after fdf_describe_device).  Everything is exact integer arithmetic and the
+ * result is a pure function of the inputs.
+ *
+ * Sets.  A set is what fdf_describe_device leaves on the device: 32 bytes per point and an
+ * offsets array.  Frame f of the query set owns the indices [qo[f], min(qo[f+1], q_cap)), frame
+ * f of the train set [to[f], min(to[f+1], t_cap)); frame f of the one is matched against frame
+ * f of the other and against nothing else.  The two sets may share one descriptor array:
+ * matching every frame of a batch of F against the next one is d_q_offsets = offs,
+ * d_t_offsets = offs + 1, n_frames = F - 1 over the same d_desc.  Indices in the result are
+ * global indices into the train arrays, not frame-relative; q_cap and t_cap must be below
+ * 2^32 - 1 (FDF_ERR_ARG).
+ *
+ * Distance.  d(i, j) = the number of set bits of the XOR of the two descriptors, 0..256.
+ *
+ * Candidates of query i: every train index of its frame; with both point arrays given, only
+ * those with |x_q - x_t| <= max_dx and |y_q - y_t| <= max_dy (unsigned absolute differences,
+ * no wrap).  Both point arrays NULL: no window, max_dx and max_dy are ignored; one NULL and
+ * one not: FDF_ERR_ARG.  With a window the train points of a frame must have non-decreasing
+ * y, which the raster order of the detector and of fdf_select_device guarantees; queries may
+ * come in any order.  A train frame that breaks the order gets unspecified matches, but even
+ * then every reported index lies in that frame's train range or is FDF_MATCH_NONE, and no
+ * access leaves the buffers.
+ *
+ * Result for query i.  index = the candidate with the smallest (d, j) in lexicographic order
+ * (ties go to the lowest index), distance = its d, second = the smallest d over the candidates
+ * other than index (it may equal distance).  No candidate: {FDF_MATCH_NONE, 0xFFFF, 0xFFFF};
+ * one candidate: second = 0xFFFF.  Entries outside [qo[0], min(qo[n_frames], q_cap)) are not
+ * written.
+ *
+ * Filter.  fdf_match_filter_device writes, for every i in [qo[0], min(qo[n_frames], q_cap)) and
+ * for no other byte, d_keep[i] = 1 if all of these hold and 0 otherwise:
+ *   index != FDF_MATCH_NONE;
+ *   distance <= max_distance (any max_distance >= 256 disables this test);
+ *   the ratio test: ratio_den == 0 (off), or second == 0xFFFF, or distance * ratio_den <
+ *   second * ratio_num in uint32 (Lowe's 0.75 is 3 / 4; both terms <= 65535, FDF_ERR_ARG
+ *   otherwise);
+ *   the cross-check: d_reverse == NULL (off), or index < t_cap and d_reverse[index].index == i,
+ *   where d_reverse (t_cap entries) is the result of the same match with the sets swapped.
+ * An index a match holds is compared with t_cap before d_reverse is read at it.
+ *
+ * fdf_match_device, fdf_match_filter_device: asynchronous on `stream` (NULL = the HIP null
+ * stream); they take no context lock and use no context workspace, they only bind the
+ * context's device; nothing is allocated and nothing returns to the host.  FDF_ERR_ARG,
+ * synchronously and with nothing launched: a NULL required pointer, n_frames > 65535, a cap of
+ * 2^32 - 1 or more, a descriptor pointer that is not 4-byte aligned, a match array that is not
+ * 8-byte aligned.  n_frames == 0 or q_cap == 0: FDF_OK, nothing written.  d_t_desc may be NULL
+ * when t_cap == 0.
+ *
+ * fdf_match_points: one pair of host sets, synchronous; nothing about the points is rejected
+ * except one array without the other; n_q == 0 is FDF_OK.  Copies through device buffers
+ * allocated and freed by the call and runs the same kernel; the context's workspace and
+ * retained result are untouched, so fdf_fetch_last stays valid.
+ */
+#define FDF_MATCH_NONE 0xFFFFFFFFu      /* index of a query with no candidate */
+#define FDF_MATCH_NO_DISTANCE 0xFFFFu   /* distance / second when there is none */
+typedef struct fdf_match {
+    uint32_t index;
+    uint16_t distance;
+    uint16_t second;
+} fdf_match;
+int fdf_match_device(fdf_ctx* ctx, uint32_t n_frames, const uint8_t* d_q_desc,
+                     const fdf_point* d_q_points, uint64_t q_cap, const uint64_t* d_q_offsets,
+                     const uint8_t* d_t_desc, const fdf_point* d_t_points, uint64_t t_cap,
+                     const uint64_t* d_t_offsets, uint32_t max_dx, uint32_t max_dy,
+                     fdf_match* d_matches, void* stream);
+int fdf_match_filter_device(fdf_ctx* ctx, uint32_t n_frames, const fdf_match* d_matches,
+                            uint64_t q_cap, const uint64_t* d_q_offsets,
+                            const fdf_match* d_reverse, uint64_t t_cap, uint32_t max_distance,
+                            uint32_t ratio_num, uint32_t ratio_den, uint8_t* d_keep,
+                            void* stream);
+int fdf_match_points(fdf_ctx* ctx, const uint8_t* q_desc, const fdf_point* q_points, size_t n_q,
+                     const uint8_t* t_desc, const fdf_point* t_points, size_t n_t,
+                     uint32_t max_dx, uint32_t max_dy, fdf_match* out);
 
 /*
  * Streaming host pipeline (extension; the reference's callers detect on one

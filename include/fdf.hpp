@@ -17,6 +17,7 @@
 //   (none: callers keep the best K)  --                   fdf::select_best(points, scores, ...)
 //   (none: ORB-style callers orient) --                   fdf::keypoint_angles(img, points, ...)
 //   (none: ... and describe)         --                   fdf::keypoint_descriptors(img, points, ...)
+//   (none: ... and match)            --                   fdf::match_descriptors(q_desc, t_desc, ...)
 //
 // Where the reference panics (n < 9, n > 16, degenerate sizes) these throw fdf::Error.
 // Each thread lazily owns one device context per HIP device (device 0 unless
@@ -266,6 +267,43 @@ inline std::vector<uint8_t> keypoint_descriptors(const GrayView& img,
                                                  const std::array<int8_t, 1024>* pattern = nullptr,
                                                  uint32_t n_bins = 30, bool smooth = true) {
     return keypoint_descriptors(img, points, angles, pattern, n_bins, smooth, thread_context());
+}
+
+// Brute-force Hamming matching of two descriptor sets (extension, fdf_match_points): for
+// every query descriptor (32 bytes each) the index of the nearest train descriptor (ties: the
+// lowest index; FDF_MATCH_NONE without a candidate), its distance and the distance of the
+// second nearest (0xFFFF: none).  With both point lists (one point per descriptor, the train
+// points' y non-decreasing) only train points with |dx| <= max_dx and |dy| <= max_dy are
+// candidates; without them max_dx and max_dy are ignored.
+using Match = fdf_match;
+inline std::vector<Match> match_descriptors(const std::vector<uint8_t>& q_desc,
+                                            const std::vector<uint8_t>& t_desc,
+                                            const std::vector<Point>* q_points,
+                                            const std::vector<Point>* t_points, uint32_t max_dx,
+                                            uint32_t max_dy, Context& ctx) {
+    if (q_desc.size() % 32 || t_desc.size() % 32)
+        throw Error(FDF_ERR_ARG, "match_descriptors: 32 bytes per descriptor");
+    const size_t n_q = q_desc.size() / 32, n_t = t_desc.size() / 32;
+    if ((q_points && q_points->size() != n_q) || (t_points && t_points->size() != n_t))
+        throw Error(FDF_ERR_ARG, "match_descriptors: one point per descriptor");
+    std::vector<Match> out(n_q);
+    // an empty list is still a list: the C entry tells "no window" by NULL
+    auto pts = [](const std::vector<Point>* v) -> const fdf_point* {
+        static const fdf_point none = {0, 0};
+        if (!v) return nullptr;
+        return v->empty() ? &none : reinterpret_cast<const fdf_point*>(v->data());
+    };
+    check(fdf_match_points(ctx.get(), q_desc.data(), pts(q_points), n_q, t_desc.data(),
+                           pts(t_points), n_t, max_dx, max_dy, out.data()),
+          "fdf_match_points");
+    return out;
+}
+inline std::vector<Match> match_descriptors(const std::vector<uint8_t>& q_desc,
+                                            const std::vector<uint8_t>& t_desc,
+                                            const std::vector<Point>* q_points = nullptr,
+                                            const std::vector<Point>* t_points = nullptr,
+                                            uint32_t max_dx = 0, uint32_t max_dy = 0) {
+    return match_descriptors(q_desc, t_desc, q_points, t_points, max_dx, max_dy, thread_context());
 }
 
 inline std::vector<Point> detect(const GrayView& img, const Config& config) {
