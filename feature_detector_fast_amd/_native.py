@@ -44,7 +44,8 @@ EXPORTED_SYMBOLS = (
     "fdf_select_device", "fdf_select_points", "fdf_orient_disc", "fdf_orient_device",
     "fdf_orient_points", "fdf_brief_pattern", "fdf_brief_steer", "fdf_smooth_device",
     "fdf_describe_device", "fdf_describe_points", "fdf_match_device",
-    "fdf_match_filter_device", "fdf_match_points",
+    "fdf_match_filter_device", "fdf_match_points", "fdf_resize_taps", "fdf_resize_device",
+    "fdf_resize_frame", "fdf_pyramid_plan", "fdf_pyramid_taps", "fdf_pyramid_device",
 )
 
 
@@ -60,6 +61,13 @@ class FdfMatch(ctypes.Structure):
     """include/fdf.h fdf_match: 8 bytes."""
     _fields_ = [("index", ctypes.c_uint32), ("distance", ctypes.c_uint16),
                 ("second", ctypes.c_uint16)]
+
+
+class FdfPyramidLevel(ctypes.Structure):
+    """include/fdf.h fdf_pyramid_level: 40 bytes."""
+    _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32),
+                ("frame_stride_bytes", ctypes.c_uint64), ("offset_bytes", ctypes.c_uint64),
+                ("xtaps_offset", ctypes.c_uint64), ("ytaps_offset", ctypes.c_uint64)]
 
 
 FDF_MATCH_NONE = 0xFFFFFFFF
@@ -225,6 +233,20 @@ def load():
     lib.fdf_match_filter_device.argtypes = [vp, u32, vp, u64, vp, vp, u64, u32, u32, u32, vp, vp]
     lib.fdf_match_points.restype = ctypes.c_int
     lib.fdf_match_points.argtypes = [vp, vp, vp, sz, vp, vp, sz, u32, u32, vp]
+    lib.fdf_resize_taps.restype = ctypes.c_int
+    lib.fdf_resize_taps.argtypes = [u32, u32, vp]
+    lib.fdf_resize_device.restype = ctypes.c_int
+    lib.fdf_resize_device.argtypes = [vp, vp, u32, u32, u32, u64, vp, u32, u32, u64, vp, vp, vp]
+    lib.fdf_resize_frame.restype = ctypes.c_int
+    lib.fdf_resize_frame.argtypes = [vp, vp, u32, u32, sz, vp, u32, u32, sz]
+    levelp = ctypes.POINTER(FdfPyramidLevel)
+    lib.fdf_pyramid_plan.restype = ctypes.c_int
+    lib.fdf_pyramid_plan.argtypes = [u32, u32, u32, u32, u32, u32, levelp, ctypes.POINTER(u64),
+                                     ctypes.POINTER(u64)]
+    lib.fdf_pyramid_taps.restype = ctypes.c_int
+    lib.fdf_pyramid_taps.argtypes = [levelp, u32, u32, u32, vp]
+    lib.fdf_pyramid_device.restype = ctypes.c_int
+    lib.fdf_pyramid_device.argtypes = [vp, vp, u32, u64, levelp, u32, vp, vp, vp]
     del u8p
     _lib = lib
     return lib

@@ -346,6 +346,30 @@ struct SmoothParams {
 };
 hipError_t launch_smooth(const SmoothParams& p, hipStream_t stream);
 
+// Exact bilinear resize (fdf_resize.hip; fdf_resize_device, fdf_pyramid_device).
+constexpr int kResizeThreads = 256;
+constexpr uint32_t kResizeOne = 2048;                // a weight of 1: taps hold frac * 2048
+constexpr uint32_t kResizeShift = 22;                // two weights of 11 bits
+constexpr uint32_t kResizeHalf = 1u << (kResizeShift - 1);
+constexpr uint32_t kResizeMaxSide = 65535;           // a tap word's index: i0 << 12 | q
+constexpr uint32_t kResizeMinSrcWidth = 8;           // the strip kernel loads 8 bytes of a row
+constexpr uint32_t kResizeStripRows = 64;            // rows a thread walks when the grid is large
+struct ResizeParams {
+    const uint8_t* src;          // frame f at src + f * src_stride, src_w * src_h bytes
+    uint64_t src_stride;
+    uint8_t* dst;                // frame f at dst + f * dst_stride, dst_w * dst_h bytes
+    uint64_t dst_stride;
+    const uint32_t* xtaps;       // dst_w words (fdf_resize_taps), clamped on the device
+    const uint32_t* ytaps;       // dst_h words
+    uint32_t n_frames, src_w, src_h, dst_w, dst_h;
+    uint32_t groups;             // ceil(dst_w / 4): a thread owns 4 destination columns
+    uint32_t strip_rows, strips; // rows a thread walks; strips = ceil(dst_h / strip_rows)
+};
+// The strip kernel's shapes: a horizontal ratio of at most 2 (every other shape: a thread per
+// pixel, the same integers).
+bool resize_fast_path(uint32_t src_w, uint32_t dst_w);
+hipError_t launch_resize(const ResizeParams& p, hipStream_t stream);
+
 // Brute-force Hamming matching of the 256-bit descriptors (fdf_match.hip; fdf_match_device,
 // fdf_match_filter_device).
 constexpr int kMatchThreads = 256;                    // queries of a workgroup pass

@@ -1,6 +1,6 @@
 // fdf_stages.cpp -- the C ABI of the stages behind the detector (extensions: the reference
 // returns points only): best-K selection, orientation, steered BRIEF descriptors, box
-// smoothing and descriptor matching.  Each has an asynchronous _device entry on the caller's stream and memory and a
+// smoothing, descriptor matching and the resize behind the scale pyramid.  Each has an asynchronous _device entry on the caller's stream and memory and a
 // host convenience _points entry.  Of a context they use the device, the mutex and the
 // stream only: its workspace and retained result (fdf_fetch_last) are not touched.
 #include <algorithm>
@@ -56,6 +56,15 @@ public:
                  ? hipMemcpyAsync(at(p), data, p.count, hipMemcpyHostToDevice, ctx_->stream)
                  : hipMemcpy2DAsync(at(p), width, data, stride_bytes, width, height,
                                     hipMemcpyHostToDevice, ctx_->stream);
+    }
+    // a packed device frame to rows `stride_bytes` apart
+    void download_frame(uint8_t* out, Part<uint8_t> p, uint32_t width, uint32_t height,
+                        size_t stride_bytes) {
+        if (!ok()) return;
+        e_ = stride_bytes == width
+                 ? hipMemcpyAsync(out, at(p), p.count, hipMemcpyDeviceToHost, ctx_->stream)
+                 : hipMemcpy2DAsync(out, stride_bytes, at(p), width, width, height,
+                                    hipMemcpyDeviceToHost, ctx_->stream);
     }
     void upload_one_frame(Part<uint64_t> p, uint64_t n_points) {    // offsets {0, n_points}
         one_frame_[1] = n_points;
@@ -548,6 +557,206 @@ int fdf_describe_points(fdf_ctx* ctx, const uint8_t* data, uint32_t width, uint3
                                 a.at(d_desc), ctx->stream));
     a.download(out_desc, d_desc, d_desc.count);
     return a.close();
+}
+
+// ---- exact bilinear resize and the scale pyramid (fdf_resize.hip) ---------------------------
+
+int fdf_resize_taps(uint32_t src_len, uint32_t dst_len, uint32_t* taps) {
+    if (!taps) return FDF_ERR_ARG;
+    if (src_len == 0 || dst_len == 0 || src_len > fdfk::kResizeMaxSide) return FDF_ERR_SIZE;
+    const int64_t S = src_len, D = dst_len;
+    for (int64_t i = 0; i < D; ++i) {
+        const int64_t N = (2 * i + 1) * S - D;          // the source position is N / (2 D)
+        int64_t i0 = 0, q = 0;
+        if (N >= 0) {
+            i0 = N / (2 * D);
+            q = (4096 * (N % (2 * D)) + 2 * D) / (4 * D);   // frac * 2048, rounded half up
+        }
+        if (i0 >= S - 1) {
+            i0 = S > 1 ? S - 2 : 0;
+            q = S > 1 ? fdfk::kResizeOne : 0;
+        }
+        taps[i] = (uint32_t)(i0 << 12 | q);
+    }
+    return FDF_OK;
+}
+
+namespace {
+
+// What fdf_resize_device checks of its shapes and strides; *src_stride and *dst_stride are the
+// frames' when the call is valid.
+int check_resize(uint32_t n_frames, uint32_t src_w, uint32_t src_h, uint64_t src_stride_bytes,
+                 uint32_t dst_w, uint32_t dst_h, uint64_t dst_stride_bytes, uint64_t* src_stride,
+                 uint64_t* dst_stride) {
+    const uint64_t src_bytes = (uint64_t)src_w * src_h, dst_bytes = (uint64_t)dst_w * dst_h;
+    if (n_frames > 65535u) return FDF_ERR_ARG;
+    if (src_bytes == 0 || src_bytes > fdfk::kOrientMaxPixels || dst_bytes == 0 ||
+        dst_bytes > fdfk::kOrientMaxPixels || src_w > fdfk::kResizeMaxSide ||
+        src_h > fdfk::kResizeMaxSide)
+        return FDF_ERR_SIZE;
+    *src_stride = frame_stride(n_frames, src_stride_bytes, src_bytes);
+    *dst_stride = frame_stride(n_frames, dst_stride_bytes, dst_bytes);
+    return *src_stride >= src_bytes && *dst_stride >= dst_bytes ? FDF_OK : FDF_ERR_ARG;
+}
+
+hipError_t resize_enqueue(const uint8_t* d_src, uint32_t n_frames, uint32_t src_w, uint32_t src_h,
+                          uint64_t src_stride, uint8_t* d_dst, uint32_t dst_w, uint32_t dst_h,
+                          uint64_t dst_stride, const uint32_t* d_xtaps, const uint32_t* d_ytaps,
+                          hipStream_t s) {
+    fdfk::ResizeParams p{};
+    p.src = d_src;
+    p.src_stride = src_stride;
+    p.dst = d_dst;
+    p.dst_stride = dst_stride;
+    p.xtaps = d_xtaps;
+    p.ytaps = d_ytaps;
+    p.n_frames = n_frames;
+    p.src_w = src_w;
+    p.src_h = src_h;
+    p.dst_w = dst_w;
+    p.dst_h = dst_h;
+    p.groups = (dst_w + 3) / 4;
+    // the tallest strips that still leave 16 waves per CU
+    p.strip_rows = fdfk::kResizeStripRows;
+    while (p.strip_rows > 8 &&
+           (uint64_t)p.groups * ((dst_h + p.strip_rows - 1) / p.strip_rows) * n_frames < 256 * 1024)
+        p.strip_rows /= 2;
+    p.strips = (dst_h + p.strip_rows - 1) / p.strip_rows;
+    return fdfk::launch_resize(p, s);
+}
+
+// The sizes of a plan: level l from level l - 1 by the factor num / den, rounded to nearest.
+int pyramid_sizes(uint32_t base_w, uint32_t base_h, uint32_t num, uint32_t den, uint32_t n_levels,
+                  uint32_t* w, uint32_t* h) {
+    if (den == 0 || num <= den || n_levels == 0 || n_levels > 32) return FDF_ERR_ARG;
+    if (base_w == 0 || base_h == 0 || base_w > fdfk::kResizeMaxSide ||
+        base_h > fdfk::kResizeMaxSide)
+        return FDF_ERR_SIZE;
+    w[0] = base_w;
+    h[0] = base_h;
+    for (uint32_t l = 1; l < n_levels; ++l) {
+        w[l] = (uint32_t)(((uint64_t)w[l - 1] * den + num / 2) / num);
+        h[l] = (uint32_t)(((uint64_t)h[l - 1] * den + num / 2) / num);
+        if (w[l] == 0 || h[l] == 0) return FDF_ERR_SIZE;
+    }
+    return FDF_OK;
+}
+
+}  // namespace
+
+int fdf_resize_device(fdf_ctx* ctx, const uint8_t* d_src, uint32_t n_frames, uint32_t src_w,
+                      uint32_t src_h, uint64_t src_frame_stride_bytes, uint8_t* d_dst,
+                      uint32_t dst_w, uint32_t dst_h, uint64_t dst_frame_stride_bytes,
+                      const uint32_t* d_xtaps, const uint32_t* d_ytaps, void* stream) {
+    if (!ctx) return FDF_ERR_ARG;
+    uint64_t ss = 0, ds = 0;
+    const bool ptrs = d_src && d_dst && d_xtaps && d_ytaps;
+    const int rc = check_resize(n_frames, src_w, src_h, src_frame_stride_bytes, dst_w, dst_h,
+                                dst_frame_stride_bytes, &ss, &ds);
+    if (rc == FDF_ERR_SIZE || n_frames > 65535u) return rc;
+    if (n_frames == 0) return FDF_OK;
+    if (!ptrs || rc) return FDF_ERR_ARG;
+    DeviceGuard guard(ctx->device);
+    return status_of(resize_enqueue(d_src, n_frames, src_w, src_h, ss, d_dst, dst_w, dst_h, ds,
+                                    d_xtaps, d_ytaps, reinterpret_cast<hipStream_t>(stream)));
+}
+
+int fdf_resize_frame(fdf_ctx* ctx, const uint8_t* data, uint32_t width, uint32_t height,
+                     size_t stride_bytes, uint8_t* out, uint32_t dst_w, uint32_t dst_h,
+                     size_t out_stride_bytes) {
+    if (!ctx) return FDF_ERR_ARG;
+    uint64_t ss = 0, ds = 0;
+    const int rc = check_resize(1, width, height, 0, dst_w, dst_h, 0, &ss, &ds);
+    if (rc) return rc;
+    if (!data || !out || stride_bytes < width || out_stride_bytes < dst_w) return FDF_ERR_ARG;
+    std::vector<uint32_t> taps((size_t)dst_w + dst_h);  // an asynchronous copy's source
+    if (fdf_resize_taps(width, dst_w, taps.data()) != FDF_OK ||
+        fdf_resize_taps(height, dst_h, taps.data() + dst_w) != FDF_OK)
+        return FDF_ERR_SIZE;
+    Arena a(ctx);
+    const auto d_src = a.part<uint8_t>(ss);
+    const auto d_dst = a.part<uint8_t>(ds);
+    const auto d_taps = a.part<uint32_t>(taps.size());
+    if (a.open() != FDF_OK) return FDF_ERR_ALLOC;
+    a.upload_frame(d_src, data, width, height, stride_bytes);
+    a.upload(d_taps, taps.data());
+    if (a.ok())
+        a.note(resize_enqueue(a.at(d_src), 1, width, height, ss, a.at(d_dst), dst_w, dst_h, ds,
+                              a.at(d_taps), a.at(d_taps) + dst_w, ctx->stream));
+    a.download_frame(out, d_dst, dst_w, dst_h, out_stride_bytes);
+    return a.close();
+}
+
+int fdf_pyramid_plan(uint32_t base_w, uint32_t base_h, uint32_t num, uint32_t den,
+                     uint32_t n_levels, uint32_t n_frames, fdf_pyramid_level* levels,
+                     uint64_t* total_bytes, uint64_t* total_taps) {
+    if (!levels || n_frames > 65535u) return FDF_ERR_ARG;
+    uint32_t w[32], h[32];
+    const int rc = pyramid_sizes(base_w, base_h, num, den, n_levels, w, h);
+    if (rc) return rc;
+    uint64_t bytes = 0, taps = 0;
+    for (uint32_t l = 0; l < n_levels; ++l) {
+        fdf_pyramid_level& L = levels[l];
+        L = fdf_pyramid_level{};
+        L.width = w[l];
+        L.height = h[l];
+        if (l == 0) continue;                        // the caller's frames: nothing of the buffer
+        L.frame_stride_bytes = (uint64_t)w[l] * h[l];
+        L.offset_bytes = bytes;
+        L.xtaps_offset = taps;
+        L.ytaps_offset = taps + w[l];
+        bytes += align256(L.frame_stride_bytes * n_frames);
+        taps += (uint64_t)w[l] + h[l];
+    }
+    if (total_bytes) *total_bytes = bytes;
+    if (total_taps) *total_taps = taps;
+    return FDF_OK;
+}
+
+int fdf_pyramid_taps(const fdf_pyramid_level* levels, uint32_t n_levels, uint32_t base_w,
+                     uint32_t base_h, uint32_t* taps) {
+    if (!levels || n_levels == 0 || n_levels > 32 || levels[0].width != base_w ||
+        levels[0].height != base_h || (n_levels > 1 && !taps))
+        return FDF_ERR_ARG;
+    for (uint32_t l = 1; l < n_levels; ++l) {
+        int rc = fdf_resize_taps(levels[l - 1].width, levels[l].width, taps + levels[l].xtaps_offset);
+        if (rc == FDF_OK)
+            rc = fdf_resize_taps(levels[l - 1].height, levels[l].height,
+                                 taps + levels[l].ytaps_offset);
+        if (rc) return rc;
+    }
+    return FDF_OK;
+}
+
+int fdf_pyramid_device(fdf_ctx* ctx, const uint8_t* d_frames, uint32_t n_frames,
+                       uint64_t frame_stride_bytes, const fdf_pyramid_level* levels,
+                       uint32_t n_levels, uint8_t* d_pyramid, const uint32_t* d_taps,
+                       void* stream) {
+    if (!ctx || !levels || n_levels == 0 || n_levels > 32 || n_frames > 65535u) return FDF_ERR_ARG;
+    // every level is checked before the first launch
+    uint64_t ss[32] = {0}, ds[32] = {0};
+    for (uint32_t l = 1; l < n_levels; ++l) {
+        const fdf_pyramid_level& S = levels[l - 1];
+        const fdf_pyramid_level& D = levels[l];
+        const int rc = check_resize(n_frames, S.width, S.height,
+                                    l == 1 ? frame_stride_bytes : S.frame_stride_bytes, D.width,
+                                    D.height, D.frame_stride_bytes, &ss[l], &ds[l]);
+        if (rc) return rc;
+    }
+    if (n_frames == 0 || n_levels == 1) return FDF_OK;
+    if (!d_frames || !d_pyramid || !d_taps) return FDF_ERR_ARG;
+    DeviceGuard guard(ctx->device);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    for (uint32_t l = 1; l < n_levels; ++l) {
+        const fdf_pyramid_level& S = levels[l - 1];
+        const fdf_pyramid_level& D = levels[l];
+        const uint8_t* src = l == 1 ? d_frames : d_pyramid + S.offset_bytes;
+        const hipError_t e = resize_enqueue(src, n_frames, S.width, S.height, ss[l],
+                                            d_pyramid + D.offset_bytes, D.width, D.height, ds[l],
+                                            d_taps + D.xtaps_offset, d_taps + D.ytaps_offset, s);
+        if (e != hipSuccess) return FDF_ERR_DEVICE;
+    }
+    return FDF_OK;
 }
 
 // ---- brute-force Hamming matching (fdf_match.hip) ------------------------------------------

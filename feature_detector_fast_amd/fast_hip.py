@@ -934,6 +934,329 @@ def detect_described_array(img, config, radius=15, n_bins=30, device=0):
     return pts, angles, keypoint_descriptors(arr, pts, angles, n_bins=n, device=device)
 
 
+# ---- exact bilinear resize and the scale pyramid ---------------------------------------------
+
+_MAX_SIDE = 65535                 # a tap word holds i0 << 12 | q
+_MAX_PIXELS = 0x7fffff00          # byte offsets of a frame fit an int
+
+
+def _side(v, name, top=0xffffffff):
+    n = int(v)
+    if not 1 <= n <= top:
+        raise ValueError(f"{name} must be in 1..{top}")
+    return n
+
+
+def _dst_shape(shape):
+    """(dst_h, dst_w) of a resize."""
+    try:
+        h, w = (int(v) for v in shape)
+    except (TypeError, ValueError):
+        raise TypeError("shape must be a pair (height, width) of integers") from None
+    if h < 1 or w < 1 or h * w > _MAX_PIXELS:
+        raise ValueError("the destination must have 1 <= width * height <= 2^31 - 256 pixels")
+    return h, w
+
+
+def _scale(scale):
+    try:
+        num, den = (int(v) for v in scale)
+    except (TypeError, ValueError):
+        raise TypeError("scale must be a pair (num, den) of integers") from None
+    if not (0 <= num <= 0xffffffff and 0 <= den <= 0xffffffff):
+        raise ValueError("scale terms must fit u32")
+    return num, den
+
+
+def resize_taps(src_len, dst_len):
+    """The taps of one axis of a resize from ``src_len`` to ``dst_len`` pixels
+    (fdf_resize_taps; host only, no device): (dst_len,) uint32, entry i = i0 << 12 | q with the
+    first source index i0 and the second tap's weight q of 2048."""
+    s = _side(src_len, "src_len", _MAX_SIDE)
+    d = _side(dst_len, "dst_len", _MAX_PIXELS)
+    taps = np.zeros(d, dtype=np.uint32)
+    check(_native.load().fdf_resize_taps(s, d, taps.ctypes.data), "fdf_resize_taps")
+    return taps
+
+
+def _check_taps(t, n, name):
+    if t.dim() != 1 or t.element_size() != 4 or t.is_floating_point() or \
+            not t.is_contiguous() or t.numel() < n:
+        raise ValueError(f"{name} must be a contiguous 32-bit integer tensor, one entry per "
+                         "destination index")
+
+
+def _device_taps(torch, taps, device):
+    return torch.from_numpy(np.ascontiguousarray(taps).view(np.int32)).to(device)
+
+
+def resize_device(frames, out, xtaps=None, ytaps=None, stream=None, device=None):
+    """Exact bilinear resize on the device (fdf_resize_device): ``frames`` (F, H, W) and ``out``
+    (F, h, w) uint8 tensors with contiguous frames any number of bytes apart (each its own);
+    the bytes between output frames are not written.  They must not overlap.  ``xtaps`` (w,)
+    and ``ytaps`` (h,) are 32-bit integer tensors holding resize_taps(W, w) and
+    resize_taps(H, h) (None: computed and uploaded by the call); entries are clamped on the
+    device.  Asynchronous on ``stream`` (default: torch's current stream)."""
+    import torch
+
+    _check_frames(torch, frames)
+    _check_frames(torch, out, "out")
+    f, sh, sw = frames.shape
+    of, dh, dw = out.shape
+    if of != f:
+        raise ValueError("frames and out must hold the same number of frames")
+    if f > 65535:
+        raise ValueError("at most 65535 frames")
+    for h, w, name in ((sh, sw, "frames"), (dh, dw, "out")):
+        if h < 1 or w < 1 or h * w > _MAX_PIXELS:
+            raise ValueError(f"{name}: 1 <= width * height <= 2^31 - 256 pixels")
+    if sh > _MAX_SIDE or sw > _MAX_SIDE:
+        raise ValueError("a source side is at most 65535 pixels")
+    tensors = [frames, out]
+    for t, n, name in ((xtaps, dw, "xtaps"), (ytaps, dh, "ytaps")):
+        if t is not None:
+            _check_taps(t, n, name)
+            tensors.append(t)
+    _check_one_device("resize_device", tensors)
+    if f:
+        (a0, a1), (b0, b1) = ((t.data_ptr(), t.data_ptr() + (f - 1) * t.stride(0) +
+                               t.shape[1] * t.shape[2]) for t in (frames, out))
+        if a0 < b1 and b0 < a1:
+            raise ValueError("frames and out must not overlap")
+    dev, stream = _device_stream(torch, frames, device, stream)
+    if xtaps is None:
+        xtaps = _device_taps(torch, resize_taps(sw, dw), frames.device)
+    if ytaps is None:
+        ytaps = _device_taps(torch, resize_taps(sh, dh), frames.device)
+    out_ptr, _, _, _, out_stride = _frame_args(out)
+    rc = _native.load().fdf_resize_device(
+        context(dev).handle, *_frame_args(frames), out_ptr, dw, dh, out_stride,
+        xtaps.data_ptr(), ytaps.data_ptr(), ctypes.c_void_p(stream.cuda_stream))
+    check(rc, "fdf_resize_device")
+
+
+def resize_array(img, shape, device=0):
+    """One host image resized to ``shape`` = (height, width) (fdf_resize_frame): a (height,
+    width) uint8 array, every pixel rounded once."""
+    arr = _as_pixels(img)
+    dh, dw = _dst_shape(shape)
+    h, w = arr.shape
+    if h < 1 or w < 1 or h > _MAX_SIDE or w > _MAX_SIDE or h * w > _MAX_PIXELS:
+        raise ValueError("the image must have sides in 1..65535 and at most 2^31 - 256 pixels")
+    out = np.zeros((dh, dw), dtype=np.uint8)
+    rc = _native.load().fdf_resize_frame(context(device).handle, arr.ctypes.data, w, h,
+                                         arr.strides[0], out.ctypes.data, dw, dh, dw)
+    check(rc, "fdf_resize_frame")
+    return out
+
+
+PyramidLevel = collections.namedtuple(
+    "PyramidLevel", "width height frame_stride_bytes offset_bytes xtaps_offset ytaps_offset")
+
+
+class PyramidPlan:
+    """The levels of a scale pyramid (fdf_pyramid_plan): ``levels`` is a tuple of
+    :class:`PyramidLevel`, level 0 the caller's frames; ``total_bytes`` is the size of the
+    buffer that holds the levels >= 1 of ``n_frames`` frames, ``total_taps`` the entries of the
+    taps array :meth:`taps` returns."""
+
+    def __init__(self, c_levels, n_frames, scale, total_bytes, total_taps):
+        self._c = c_levels
+        self.n_frames = n_frames
+        self.scale = scale
+        self.total_bytes = total_bytes
+        self.total_taps = total_taps
+        self.levels = tuple(PyramidLevel(*(getattr(L, name) for name in PyramidLevel._fields))
+                            for L in c_levels)
+
+    def __len__(self):
+        return len(self.levels)
+
+    def taps(self):
+        """The x and y taps of every level >= 1 (fdf_pyramid_taps): (total_taps,) uint32."""
+        taps = np.zeros(self.total_taps, dtype=np.uint32)
+        base = self.levels[0]
+        check(_native.load().fdf_pyramid_taps(self._c, len(self.levels), base.width, base.height,
+                                              taps.ctypes.data if taps.size else None),
+              "fdf_pyramid_taps")
+        return taps
+
+
+def pyramid_plan(shape, n_levels=8, scale=(6, 5), n_frames=1):
+    """The plan of an ``n_levels`` pyramid over ``n_frames`` frames of ``shape`` = (height,
+    width) at the factor ``scale`` = (num, den) > 1 between levels (fdf_pyramid_plan; host only,
+    no device): w_l = (w_(l-1) * den + num // 2) // num.  A factor that is not above 1 or a
+    level count outside 1..32 raises FdfError(FDF_ERR_ARG), a level with a zero dimension
+    FdfError(FDF_ERR_SIZE)."""
+    try:
+        h, w = (int(v) for v in shape)
+    except (TypeError, ValueError):
+        raise TypeError("shape must be a pair (height, width) of integers") from None
+    num, den = _scale(scale)
+    n, f = int(n_levels), int(n_frames)
+    if not (0 <= h <= 0xffffffff and 0 <= w <= 0xffffffff and 0 <= n <= 0xffffffff and
+            0 <= f <= 0xffffffff):
+        raise ValueError("sizes and counts must fit u32")
+    c_levels = (_native.FdfPyramidLevel * max(1, min(n, 32)))()
+    total_bytes, total_taps = ctypes.c_uint64(), ctypes.c_uint64()
+    check(_native.load().fdf_pyramid_plan(w, h, num, den, n, f, c_levels,
+                                          ctypes.byref(total_bytes), ctypes.byref(total_taps)),
+          "fdf_pyramid_plan")
+    return PyramidPlan(c_levels, f, (num, den), total_bytes.value, total_taps.value)
+
+
+def pyramid_device(frames, plan, buffer, taps, stream=None, device=None):
+    """Every level >= 1 of ``plan`` for the (F, H, W) uint8 ``frames`` (contiguous frames any
+    number of bytes apart, F <= plan.n_frames), on the device (fdf_pyramid_device): one resize
+    per level in stream order, each from the level before.  ``buffer``: a contiguous uint8
+    tensor of at least plan.total_bytes bytes; ``taps``: a 32-bit integer tensor holding
+    plan.taps().  Asynchronous on ``stream`` (default: torch's current stream)."""
+    import torch
+
+    if not isinstance(plan, PyramidPlan):
+        raise TypeError("plan must be a PyramidPlan (pyramid_plan)")
+    _check_frames(torch, frames)
+    f, h, w = frames.shape
+    if (w, h) != (plan.levels[0].width, plan.levels[0].height):
+        raise ValueError("frames do not have the plan's level-0 size")
+    if f > plan.n_frames:
+        raise ValueError("more frames than the plan was made for")
+    if buffer.dtype != torch.uint8 or not buffer.is_contiguous() or \
+            buffer.numel() < plan.total_bytes:
+        raise ValueError("buffer must be a contiguous uint8 tensor of plan.total_bytes bytes")
+    _check_taps(taps, plan.total_taps, "taps")
+    _check_one_device("pyramid_device", [frames, buffer, taps])
+    dev, stream = _device_stream(torch, frames, device, stream)
+    ptr, _, _, _, stride = _frame_args(frames)
+    rc = _native.load().fdf_pyramid_device(
+        context(dev).handle, ptr, f, stride, plan._c, len(plan), buffer.data_ptr(),
+        taps.data_ptr(), ctypes.c_void_p(stream.cuda_stream))
+    check(rc, "fdf_pyramid_device")
+
+
+class Pyramid:
+    """The scale pyramid of device-resident ``frames`` ((F, H, W) uint8): the plan, its taps on
+    the device and one buffer for the levels >= 1.  ``level(l)`` is a contiguous (F, h_l, w_l)
+    uint8 view usable by detect_device, smooth_device, orient_device and describe_device;
+    ``level(0)`` is ``frames`` itself.  ``build()`` (run by the constructor unless
+    ``build=False``) enqueues the resizes; call it again after the frames change."""
+
+    def __init__(self, frames, n_levels=8, scale=(6, 5), stream=None, build=True):
+        import torch
+
+        _check_frames(torch, frames)
+        if not frames.is_cuda:
+            raise ValueError("Pyramid needs a CUDA (HIP) tensor")
+        f, h, w = frames.shape
+        self.frames = frames
+        self.plan = pyramid_plan((h, w), n_levels, scale, f)
+        self.taps = _device_taps(torch, self.plan.taps(), frames.device)
+        self.buffer = torch.empty(max(self.plan.total_bytes, 1), dtype=torch.uint8,
+                                  device=frames.device)
+        if build:
+            self.build(stream)
+
+    def __len__(self):
+        return len(self.plan)
+
+    def build(self, stream=None):
+        pyramid_device(self.frames, self.plan, self.buffer, self.taps, stream=stream)
+
+    def level(self, l):
+        if not 0 <= l < len(self.plan):
+            raise IndexError("no such level")
+        if l == 0:
+            return self.frames
+        L = self.plan.levels[l]
+        f = self.frames.shape[0]
+        n = f * L.frame_stride_bytes
+        return self.buffer[L.offset_bytes:L.offset_bytes + n].view(f, L.height, L.width)
+
+
+MultiscaleKeypoints = collections.namedtuple(
+    "MultiscaleKeypoints", "level points points0 scores angles descriptors sizes")
+
+
+def detect_multiscale_array(img, config, n_levels=8, scale=(6, 5), cell=None, k=None, radius=15,
+                            n_bins=30, device=0):
+    """The keypoints of one host image over its scale pyramid: the image goes to the device
+    once, the pyramid is built there (:class:`Pyramid`) and every level runs the device chain
+    detect, score, (with ``cell`` = (cell_w, cell_h) and ``k``: best-k selection per cell,)
+    orient on the level, describe on its 5 x 5 smoothed copy (default pattern, ``n_bins``
+    rotations).  Returns :class:`MultiscaleKeypoints`, ordered by level, then raster:
+    ``level`` (K,) int32, ``points`` (K, 2) uint32 level coordinates, ``points0`` (K, 2) float32
+    level-0 coordinates ((x_l + 0.5) * w_0 / w_l - 0.5 per axis, in float64, rounded once),
+    ``scores`` (K,) uint16, ``angles`` (K,) float32, ``descriptors`` (K, 32) uint8 and ``sizes``,
+    the (width, height) of every level.  Levels too small to hold a keypoint (a side below 7)
+    contribute none."""
+    import torch
+
+    if (cell is None) != (k is None):
+        raise ValueError("cell and k go together")
+    if cell is not None:
+        cw, ch, k = _cell_k(cell, k)
+        cell = (cw, ch)
+    r = _radius(radius)
+    bins = _n_bins(n_bins)
+    arr = _as_pixels(img)
+    h0, w0 = arr.shape
+    plan = pyramid_plan((h0, w0), n_levels, scale, 1)   # the plan's errors before any device call
+    _to_c_config(config)
+    dev = torch.device("cuda", int(device))
+    with torch.cuda.device(dev):
+        frames = torch.from_numpy(np.ascontiguousarray(arr)[None].copy()).to(dev)
+        pyr = Pyramid(frames, n_levels, scale)
+        table = torch.from_numpy(brief_steer(brief_pattern(), bins)).to(dev)
+        out = {name: [] for name in ("level", "points", "points0", "scores", "angles",
+                                     "descriptors")}
+        for l, L in enumerate(plan.levels):
+            w, h = L.width, L.height
+            if w < 7 or h < 7:
+                continue
+            level = pyr.level(l)
+            cap = capacity_guess(w * h)
+            offs = torch.zeros(2, dtype=torch.int64, device=dev)
+            while True:
+                pts = torch.zeros((cap, 2), dtype=torch.int32, device=dev)
+                detect_device(level, config, pts, offs)
+                total = int(offs[1])
+                if total <= cap:
+                    break
+                cap = total
+            if total == 0:
+                continue
+            pts = pts[:total]
+            scores = torch.zeros(total, dtype=torch.int16, device=dev)
+            score_device(level, config, pts, offs, scores)
+            if cell is not None:
+                sel = torch.zeros((total, 2), dtype=torch.int32, device=dev)
+                sel_scores = torch.zeros(total, dtype=torch.int16, device=dev)
+                sel_offs = torch.zeros(2, dtype=torch.int64, device=dev)
+                select_device(pts, scores, offs, (h, w), cell, k, sel, sel_scores, sel_offs)
+                total = int(sel_offs[1])
+                pts, scores, offs = sel[:total], sel_scores[:total], sel_offs
+            angles = torch.zeros(total, dtype=torch.float32, device=dev)
+            orient_device(level, pts, offs, angles, radius=r)
+            smoothed = torch.empty_like(level)
+            smooth_device(level, smoothed)
+            desc = torch.zeros((total, 32), dtype=torch.uint8, device=dev)
+            describe_device(smoothed, pts, offs, desc, table, bins, angles=angles)
+            p = pts.cpu().numpy().view(np.uint32)
+            out["level"].append(np.full(total, l, dtype=np.int32))
+            out["points"].append(p)
+            out["points0"].append(((p.astype(np.float64) + 0.5) *
+                                   np.array([w0, h0], dtype=np.float64) /
+                                   np.array([w, h], dtype=np.float64) - 0.5).astype(np.float32))
+            out["scores"].append(scores.cpu().numpy().view(np.uint16))
+            out["angles"].append(angles.cpu().numpy())
+            out["descriptors"].append(desc.cpu().numpy())
+    empty = {"level": np.zeros(0, np.int32), "points": np.zeros((0, 2), np.uint32),
+             "points0": np.zeros((0, 2), np.float32), "scores": np.zeros(0, np.uint16),
+             "angles": np.zeros(0, np.float32), "descriptors": np.zeros((0, 32), np.uint8)}
+    merged = {name: np.concatenate(v) if v else empty[name] for name, v in out.items()}
+    return MultiscaleKeypoints(sizes=tuple((L.width, L.height) for L in plan.levels), **merged)
+
+
 # include/fdf.h fdf_match as a numpy record; the (n, 2) 32-bit layout of the device wrappers
 # holds the same 8 bytes: column 0 the index, column 1 distance | second << 16.
 MATCH_DTYPE = np.dtype([("index", "<u4"), ("distance", "<u2"), ("second", "<u2")])
@@ -1160,6 +1483,9 @@ __all__ = ["NORTH", "EAST", "SOUTH", "WEST", "circle", "calculate_offsets", "con
            "orient_disc", "orient_device", "keypoint_angles", "detect_oriented_array",
            "brief_pattern", "brief_steer", "smooth_device", "describe_device",
            "keypoint_descriptors", "detect_described_array",
+           "resize_taps", "resize_device", "resize_array", "PyramidLevel", "PyramidPlan",
+           "pyramid_plan", "pyramid_device", "Pyramid", "MultiscaleKeypoints",
+           "detect_multiscale_array",
            "MATCH_DTYPE", "MATCH_NONE", "MATCH_NO_DISTANCE", "match_device",
            "match_filter_device", "unpack_matches", "match_descriptors",
            "detect_rgb_array", "detector_rgb", "rgb_to_luma", "detect_device_rgb",

@@ -35,7 +35,9 @@ extern "C" {
  * without changing any existing function, which is backward compatible; so were
  * fdf_orient_disc, fdf_orient_device and fdf_orient_points, and fdf_brief_pattern,
  * fdf_brief_steer, fdf_smooth_device, fdf_describe_device and fdf_describe_points, and
- * fdf_match_device, fdf_match_filter_device and fdf_match_points. */
+ * fdf_match_device, fdf_match_filter_device and fdf_match_points, and fdf_resize_taps,
+ * fdf_resize_device, fdf_resize_frame, fdf_pyramid_plan, fdf_pyramid_taps and
+ * fdf_pyramid_device. */
 #define FDF_ABI_VERSION 6
 
 /* Status codes.  Shapes the reference maps to an empty Vec return FDF_OK with 0 points. */
@@ -589,6 +591,92 @@ int fdf_match_filter_device(fdf_ctx* ctx, uint32_t n_frames, const fdf_match* d_
 int fdf_match_points(fdf_ctx* ctx, const uint8_t* q_desc, const fdf_point* q_points, size_t n_q,
                      const uint8_t* t_desc, const fdf_point* t_points, size_t n_t,
                      uint32_t max_dx, uint32_t max_dy, fdf_match* out);
+
+/*
+ * Exact bilinear resize and the scale pyramid (extension: the reference detects at one scale;
+ * ORB-style callers run the chain above over a pyramid, 8 levels at 1.2 by default, each level
+ * resized from the one before).  Everything is integer-exact.  These are not OpenCV's bits: its
+ * 8-bit path truncates between the two passes; no parity with it is claimed.
+ *
+ * Taps of one axis.  For a source length S >= 1, a destination length D >= 1 and the destination
+ * index i, the centre-aligned source position is N / (2 D) with N = (2 i + 1) S - D, in 64-bit
+ * integers (no libm).  N < 0: i0 = 0, q = 0.  Otherwise i0 = N / (2 D), r = N % (2 D) and
+ * q = (4096 r + 2 D) / (4 D): the fraction times 2048 rounded half up, 0..2048.  i0 >= S - 1:
+ * i0 = S - 2 and q = 2048 (S = 1: i0 = 0, q = 0).  The second tap is i1 = min(i0 + 1, S - 1).
+ * One uint32_t per destination index, i0 << 12 | q; S <= 65535.  S = 1920, D = 1600: index 0 is
+ * i0 = 0, q = 205 and index 1 is i0 = 1, q = 614.
+ *
+ * Pixel.  out(x, y) = (sum over a, b in {0, 1} of wy_b * wx_a * I(ix_a, iy_b) + 2^21) >> 22 with
+ * w_0 = 2048 - q and w_1 = q of each axis.  The sum is at most 255 * 2^22 < 2^30: one rounding,
+ * no intermediate truncation.  So D = S is the identity, S = 2 D is (a + b + c + d + 2) / 4 of
+ * each 2 x 2 block and a constant frame stays constant.  Any ratio is legal, upscaling too.
+ *
+ * Pyramid.  Level 0 is the caller's frames (never copied); for the rational factor num / den > 1
+ * (ORB's 1.2 is 6 / 5) w_l = (w_(l-1) * den + num / 2) / num and the same for h: 1920 x 1080 at
+ * 6 / 5 gives 1600 x 900, 1333 x 750, 1111 x 625, ...  Level l is resized from level l - 1.  A
+ * plan is n_levels (1..32) fdf_pyramid_level entries: the level's size, and for l >= 1 the bytes
+ * between its frames (width * height: packed), its 256-byte aligned offset into one pyramid
+ * buffer that holds the levels >= 1 of all n_frames frames, and the offsets (in entries) of its
+ * x and y taps in one taps array.  Level 0's other fields are 0.  A point of level l maps back
+ * per axis by w_0 / w_l: x_0 = (x_l + 0.5) * w_0 / w_l - 0.5.
+ *
+ * fdf_resize_taps: host only, no context; writes dst_len words.  FDF_ERR_ARG for a NULL
+ * pointer, FDF_ERR_SIZE for a zero length or src_len > 65535.
+ *
+ * fdf_resize_device: asynchronous on `stream` (NULL = the HIP null stream); like
+ * fdf_smooth_device it takes no context lock and uses no context workspace, it only binds the
+ * context's device; nothing is allocated and nothing returns to the host.  Frames may be any
+ * number of bytes apart on either side and have any alignment; the gap bytes of the output are
+ * not written; input and output must not overlap.  d_xtaps (dst_w words) and d_ytaps (dst_h
+ * words) are device copies of fdf_resize_taps' tables; every entry is clamped on the device
+ * before use (i0 <= S - 1, q <= 2048), so whatever the tables hold no access leaves the frames
+ * (the values are then unspecified).  FDF_ERR_ARG, synchronously and with nothing launched: a
+ * NULL pointer, n_frames > 65535, a frame stride below width * height when n_frames > 1.
+ * FDF_ERR_SIZE: a zero dimension, width * height above 2^31 - 256 on either side, a source
+ * side above 65535.  n_frames == 0: FDF_OK, nothing written.
+ *
+ * fdf_pyramid_plan: host only.  Fills levels[0..n_levels); *total_bytes (optional) gets the
+ * pyramid buffer's size for n_frames frames, *total_taps (optional) the taps array's entries.
+ * FDF_ERR_ARG: num <= den, den == 0, n_levels outside 1..32, n_frames > 65535, a NULL levels.
+ * FDF_ERR_SIZE: a zero base dimension or one above 65535, a level with a zero dimension.
+ * fdf_pyramid_taps: host only; writes the taps of every level >= 1 of a plan whose level 0 is
+ * base_w x base_h (FDF_ERR_ARG if it is not).
+ *
+ * fdf_pyramid_device: n_levels - 1 launches of the resize kernel in stream order, level 1 from
+ * d_frames (frames frame_stride_bytes apart), level l from level l - 1 inside d_pyramid; d_taps
+ * holds fdf_pyramid_taps' array.  Asynchronous, as fdf_resize_device; every level is checked
+ * before the first launch.  n_levels == 1: FDF_OK, nothing to do.
+ *
+ * fdf_resize_frame: one host frame (rows stride_bytes apart) to one host frame (rows
+ * out_stride_bytes apart), synchronous.  Copies through device buffers allocated and freed by
+ * the call and runs the same kernel; the context's workspace and retained result are untouched,
+ * so fdf_fetch_last stays valid.
+ */
+typedef struct fdf_pyramid_level {
+    uint32_t width;
+    uint32_t height;
+    uint64_t frame_stride_bytes;   /* width * height */
+    uint64_t offset_bytes;         /* of the level's first frame in the pyramid buffer */
+    uint64_t xtaps_offset;         /* entries into the taps array: `width` words */
+    uint64_t ytaps_offset;         /* `height` words */
+} fdf_pyramid_level;
+int fdf_resize_taps(uint32_t src_len, uint32_t dst_len, uint32_t* taps);
+int fdf_resize_device(fdf_ctx* ctx, const uint8_t* d_src, uint32_t n_frames, uint32_t src_w,
+                      uint32_t src_h, uint64_t src_frame_stride_bytes, uint8_t* d_dst,
+                      uint32_t dst_w, uint32_t dst_h, uint64_t dst_frame_stride_bytes,
+                      const uint32_t* d_xtaps, const uint32_t* d_ytaps, void* stream);
+int fdf_resize_frame(fdf_ctx* ctx, const uint8_t* data, uint32_t width, uint32_t height,
+                     size_t stride_bytes, uint8_t* out, uint32_t dst_w, uint32_t dst_h,
+                     size_t out_stride_bytes);
+int fdf_pyramid_plan(uint32_t base_w, uint32_t base_h, uint32_t num, uint32_t den,
+                     uint32_t n_levels, uint32_t n_frames, fdf_pyramid_level* levels,
+                     uint64_t* total_bytes, uint64_t* total_taps);
+int fdf_pyramid_taps(const fdf_pyramid_level* levels, uint32_t n_levels, uint32_t base_w,
+                     uint32_t base_h, uint32_t* taps);
+int fdf_pyramid_device(fdf_ctx* ctx, const uint8_t* d_frames, uint32_t n_frames,
+                       uint64_t frame_stride_bytes, const fdf_pyramid_level* levels,
+                       uint32_t n_levels, uint8_t* d_pyramid, const uint32_t* d_taps,
+                       void* stream);
 
 /*
  * Streaming host pipeline (extension; the reference's callers detect on one

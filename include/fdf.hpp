@@ -18,12 +18,14 @@
 //   (none: ORB-style callers orient) --                   fdf::keypoint_angles(img, points, ...)
 //   (none: ... and describe)         --                   fdf::keypoint_descriptors(img, points, ...)
 //   (none: ... and match)            --                   fdf::match_descriptors(q_desc, t_desc, ...)
+//   (none: ... over a scale pyramid) --                   fdf::resize, fdf::pyramid_plan, fdf::build_pyramid
 //
 // Where the reference panics (n < 9, n > 16, degenerate sizes) these throw fdf::Error.
 // Each thread lazily owns one device context per HIP device (device 0 unless
 // fdf::set_device() was called), so the free functions stay pure calls like the reference's.
 #pragma once
 
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <memory>
@@ -304,6 +306,66 @@ inline std::vector<Match> match_descriptors(const std::vector<uint8_t>& q_desc,
                                             const std::vector<Point>* t_points = nullptr,
                                             uint32_t max_dx = 0, uint32_t max_dy = 0) {
     return match_descriptors(q_desc, t_desc, q_points, t_points, max_dx, max_dy, thread_context());
+}
+
+// Exact bilinear resize and the scale pyramid (extension, fdf_resize_frame and
+// fdf_pyramid_plan): integer-exact, one rounding per pixel (include/fdf.h has the rule).
+struct Image {
+    uint32_t width = 0;
+    uint32_t height = 0;
+    std::vector<uint8_t> pixels;   // rows packed
+    GrayView view() const { return GrayView(pixels.data(), width, height); }
+};
+inline Image resize(const GrayView& img, uint32_t dst_w, uint32_t dst_h, Context& ctx) {
+    Image out;
+    out.width = dst_w;
+    out.height = dst_h;
+    out.pixels.resize((size_t)dst_w * dst_h);
+    check(fdf_resize_frame(ctx.get(), img.data, img.width, img.height, img.stride,
+                           out.pixels.data(), dst_w, dst_h, dst_w),
+          "fdf_resize_frame");
+    return out;
+}
+inline Image resize(const GrayView& img, uint32_t dst_w, uint32_t dst_h) {
+    return resize(img, dst_w, dst_h, thread_context());
+}
+
+// The levels of a pyramid of `n_levels` at the factor num / den (> 1; ORB's 1.2 is 6 / 5) over
+// n_frames frames of width x height: sizes, offsets into one pyramid buffer and one taps array.
+struct PyramidPlan {
+    std::vector<fdf_pyramid_level> levels;
+    uint64_t total_bytes = 0;
+    uint64_t total_taps = 0;
+};
+inline PyramidPlan pyramid_plan(uint32_t width, uint32_t height, uint32_t n_levels = 8,
+                                uint32_t num = 6, uint32_t den = 5, uint32_t n_frames = 1) {
+    PyramidPlan plan;
+    plan.levels.resize(n_levels ? n_levels : 1);
+    check(fdf_pyramid_plan(width, height, num, den, n_levels, n_frames, plan.levels.data(),
+                           &plan.total_bytes, &plan.total_taps),
+          "fdf_pyramid_plan");
+    return plan;
+}
+
+// The pyramid of one host frame: level 0 is a packed copy of `img`, level l is level l - 1
+// resized to the plan's size.
+inline std::vector<Image> build_pyramid(const GrayView& img, uint32_t n_levels, uint32_t num,
+                                        uint32_t den, Context& ctx) {
+    const PyramidPlan plan = pyramid_plan(img.width, img.height, n_levels, num, den);
+    std::vector<Image> levels(n_levels);
+    levels[0].width = img.width;
+    levels[0].height = img.height;
+    levels[0].pixels.resize((size_t)img.width * img.height);
+    for (uint32_t y = 0; y < img.height; ++y)
+        std::copy(img.data + y * img.stride, img.data + y * img.stride + img.width,
+                  levels[0].pixels.begin() + (size_t)y * img.width);
+    for (uint32_t l = 1; l < n_levels; ++l)
+        levels[l] = resize(levels[l - 1].view(), plan.levels[l].width, plan.levels[l].height, ctx);
+    return levels;
+}
+inline std::vector<Image> build_pyramid(const GrayView& img, uint32_t n_levels = 8,
+                                        uint32_t num = 6, uint32_t den = 5) {
+    return build_pyramid(img, n_levels, num, den, thread_context());
 }
 
 inline std::vector<Point> detect(const GrayView& img, const Config& config) {
