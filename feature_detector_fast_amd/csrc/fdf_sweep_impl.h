@@ -198,13 +198,90 @@ __device__ __forceinline__ uint32_t pack_nibbles(uint32_t x) {
     return __builtin_amdgcn_perm(c, c, 0x0c0c0200u);
 }
 
+// Band-end switches, each on by default and separable for A/B builds
+// (tools/build_variant.sh NAME "-DFDF_POS_SHIFT=0" ...):
+//   FDF_POS_SHIFT     list positions are bitmap row << xbits | x instead of row * W + x
+//   FDF_RANK_2PASS    block rank prefixes stay row-relative (no third prefix pass)
+//   FDF_SELTAB_CONST  select_bit's table is a constant copied to LDS, not rebuilt per band
+//   FDF_EMIT_REGS     the max-t emit's write pass reuses the count pass's bitmap groups (the
+//                     latency unit, fdf_sweep_latency.hip, defaults it to 0: its kernels spill)
+#ifndef FDF_POS_SHIFT
+#define FDF_POS_SHIFT 1
+#endif
+#ifndef FDF_RANK_2PASS
+#define FDF_RANK_2PASS 1
+#endif
+#ifndef FDF_SELTAB_CONST
+#define FDF_SELTAB_CONST 1
+#endif
+#ifndef FDF_EMIT_REGS
+#define FDF_EMIT_REGS 1
+#endif
+
+// The 20 position bits of a score-list entry.  Shift-encoded: bitmap row << xbits | x with
+// xbits = ceil(log2 W) (per launch, wave-uniform), so the NMS passes get (row, x) back with a
+// shift and a mask where row * W + x needs a division.  Both forms are row-major, so raster
+// order -- all the rank scatter, the emit and the compaction rely on -- is the same.
+// A band's R2 = rows + 2 * halo bitmap rows fit when R2 <= 2^(20 - xbits).  2^xbits >= W, so
+// this is the stricter test of the two, but no geometry the automatic pick makes (LDS <=
+// 40 000 B, fdf_api.cpp) tells them apart: the bitmap alone takes R2 * nw * 4 bytes with
+// nw >= W / 32 > 2^(xbits - 6), so R2 < 40000 * 16 / 2^xbits < 2^20 / 2^xbits.  Only a band
+// height forced past that budget (fdf_ctx_set_band_rows, up to the 160 KB of a CU) can fit
+// row * W + x and not the shifted form; it then takes the dense tier, whose output is the
+// same.
+struct PosCode {
+#if FDF_POS_SHIFT
+    uint32_t xbits;
+#else
+    RowDiv W;
+#endif
+};
+__device__ __forceinline__ PosCode make_poscode(uint32_t W) {
+    PosCode pc;
+#if FDF_POS_SHIFT
+    pc.xbits = 32u - (uint32_t)__builtin_clz(W - 1u);   // W >= 7
+#else
+    pc.W = make_rowdiv(W);
+#endif
+    return pc;
+}
+__device__ __forceinline__ bool pos_fits(const PosCode& pc, uint32_t R2, uint32_t W) {
+#if FDF_POS_SHIFT
+    (void)W;
+    return pc.xbits <= 20u && R2 <= (1u << (20u - pc.xbits));
+#else
+    (void)pc;
+    return (uint64_t)R2 * W <= (1u << 20);
+#endif
+}
+__device__ __forceinline__ uint32_t pos_encode(const PosCode& pc, uint32_t W, uint32_t row, uint32_t x) {
+#if FDF_POS_SHIFT
+    (void)W;
+    return (row << pc.xbits) | x;
+#else
+    (void)pc;
+    // a full-rate 24-bit multiply
+    return mul_u24_s(W, row & 0x3ffu) + x;
+#endif
+}
+__device__ __forceinline__ void pos_decode(const PosCode& pc, uint32_t pos, uint32_t& row, uint32_t& x) {
+#if FDF_POS_SHIFT
+    row = pos >> pc.xbits;
+    x = pos & ((1u << pc.xbits) - 1u);
+#else
+    row = udiv(pos, pc.W);
+    x = pos - row * pc.W;
+#endif
+}
+
 struct SweepShared {
     uint32_t* pq;          // kSweepPixelQ FIFO of lane rows with candidates (kFlagNibbles:
                            // flags; low nibbles: spread_code((row - ys) << 6 | lane))
     uint32_t* stage;       // 64 pixels of the batch being issued: (row - ys) << 10 | strip column
     uint32_t* bitmap;      // band keypoints: bitmap row i = image row yb + i, words_per_row each
-    uint32_t* slist;       // NMS: the band's keypoints as (bitmap row * W + x) << 12 | score
+    uint32_t* slist;       // NMS: the band's keypoints as (list position, PosCode) << 12 | score
     uint32_t* slist_n;     // entries appended (the list, then the spill, then only counted)
+    PosCode pc;
     uint32_t slist_cap;    // kScoreListCap, or 0 when a position does not fit 20 bits
     uint32_t* spill;       // NMS: entries past slist_cap, in the band's output slot (global)
     const uint32_t* seltab;  // select_bit's table (SweepLayout::seltab)
@@ -304,9 +381,27 @@ __device__ __forceinline__ uint32_t wave_max(uint32_t v) {
 }
 
 // Position of the j-th (from 0) set bit of a 16-bit mask that has more than j set bits.
-// seltab[b] holds the positions of byte b's set bits, the k-th in nibble k (built per
-// workgroup before its sweep), so the mask needs one byte choice and one LDS read instead
-// of four halving steps.
+// seltab[b] holds the positions of byte b's set bits, the k-th in nibble k (in LDS, filled by
+// every workgroup before its sweep), so the mask needs one byte choice and one LDS read
+// instead of four halving steps.
+struct SelTab {
+    uint32_t v[256];
+};
+constexpr SelTab make_seltab() {
+    SelTab t{};
+    for (uint32_t b = 0; b < 256; ++b) {
+        uint32_t word = 0, k = 0;
+        for (uint32_t i = 0; i < 8; ++i) {
+            if ((b >> i) & 1u) word |= i << (4u * k++);
+        }
+        t.v[b] = word;
+    }
+    return t;
+}
+#if FDF_SELTAB_CONST
+// the table in device memory (1 KB): a workgroup copies it to LDS with one load per thread
+__device__ const SelTab kSelTab = make_seltab();
+#endif
 __device__ __forceinline__ uint32_t select_bit(uint32_t m, uint32_t j, const uint32_t* seltab) {
     const uint32_t c8 = (uint32_t)__popc(m & 0xffu);
     const bool hi = j >= c8;
@@ -484,8 +579,7 @@ __device__ __forceinline__ void evaluate_batch(const SweepShared& sh, UnitCtx& u
             if (is_kp) sh.stage[(q + lanes_below(bal)) & 63u] = u.lane;
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // see issue_batch
             const int src = (int)(sh.stage[u.lane] << 2);
-            // list position (bitmap row * W + x) with a full-rate 24-bit multiply
-            const uint32_t pk = ((mul_u24_s(u.src.W, (uint32_t)(y - u.yb) & 0x3ffu) + (uint32_t)x) << 12) |
+            const uint32_t pk = (pos_encode(sh.pc, u.src.W, (uint32_t)(y - u.yb), (uint32_t)x) << 12) |
                                 (kd ? 0x100u : 0u) | c;
             uint32_t nwv[4];
 #pragma unroll
@@ -519,7 +613,7 @@ __device__ __forceinline__ void evaluate_batch(const SweepShared& sh, UnitCtx& u
             if (is_kp) {
                 const uint32_t score = score_sum_abs_packed(c, w, u.t);
                 const uint32_t idx = base + lanes_below(bal);
-                const uint32_t e = ((mul_u24_s(u.src.W, (uint32_t)(y - u.yb) & 0x3ffu) + (uint32_t)x) << 12) | score;
+                const uint32_t e = (pos_encode(sh.pc, u.src.W, (uint32_t)(y - u.yb), (uint32_t)x) << 12) | score;
                 if (idx < sh.slist_cap) sh.slist[idx] = e;
                 else if (idx - sh.slist_cap < sh.spill_cap) sh.spill[idx - sh.slist_cap] = e;
             }
@@ -781,16 +875,21 @@ __device__ __forceinline__ uint32_t bits3(const uint32_t* row, int x) {
 }
 
 // Raster rank of bitmap position (row, x): keypoints before it in the band's bitmap.
-// bprefix[row * nb + k] counts the keypoints before word 4k of the row (all rows above
-// included); the position's 4-word block is one 16-byte LDS read (bitmap rows are whole
-// blocks, bitmap_words_per_row).
+// bprefix[row * nb + k] counts the keypoints before word 4k within the row and rprefix[row]
+// those of the rows above (FDF_RANK_2PASS 0: bprefix holds their sum); the position's
+// 4-word block is one 16-byte LDS read (bitmap rows are whole blocks, bitmap_words_per_row).
 __device__ __forceinline__ uint32_t bitmap_rank(const uint32_t* bitmap, const uint16_t* bprefix,
-                                                const uint32_t* /*rprefix*/, uint32_t nw,
+                                                const uint32_t* rprefix, uint32_t nw,
                                                 uint32_t nb, uint32_t row, uint32_t x) {
     static_assert(kRankBlock == 4, "one 16-byte block per rank prefix");
     const uint32_t wi = x >> 5, blk = wi / kRankBlock, j = wi % kRankBlock;
     const uint4 q = reinterpret_cast<const uint4*>(bitmap + row * nw)[blk];
     uint32_t r = bprefix[row * nb + blk];
+#if FDF_RANK_2PASS
+    r += rprefix[row];
+#else
+    (void)rprefix;
+#endif
     r += j > 0 ? (uint32_t)__popc(q.x) : 0u;
     r += j > 1 ? (uint32_t)__popc(q.y) : 0u;
     r += j > 2 ? (uint32_t)__popc(q.z) : 0u;
@@ -809,8 +908,9 @@ __device__ __forceinline__ uint32_t neighbour_bits(const uint32_t* bitmap, uint3
 }
 
 // Rank prefixes of the band's keypoint bitmap (R2 rows): bprefix[row * nb + k] = keypoints
-// before word 4k of the row, the rows above included (rprefix: the row prefixes on the
-// way).  Returns the bitmap's keypoint total (every thread).
+// before word 4k of the row, rprefix[row] = keypoints of the rows above (FDF_RANK_2PASS 0:
+// added to the block prefixes in a third pass).  Returns the bitmap's keypoint total (every
+// thread).
 __device__ uint32_t band_rank_prefixes(const uint32_t* bitmap, uint32_t R2, uint32_t nw,
                                        uint16_t* bprefix, uint32_t* rprefix, uint32_t* total) {
     const uint32_t tid = threadIdx.x, lane = tid & 63;
@@ -878,6 +978,7 @@ __device__ uint32_t band_rank_prefixes(const uint32_t* bitmap, uint32_t R2, uint
         if (lane == 0) *total = carry;
     }
     __syncthreads();
+#if !FDF_RANK_2PASS
     // block prefixes absolute (the rows above included): one read per rank (u16 holds them:
     // the ranked tiers hold at most nms_area_entries keypoints)
     {
@@ -886,6 +987,11 @@ __device__ uint32_t band_rank_prefixes(const uint32_t* bitmap, uint32_t R2, uint
             bprefix[i] = (uint16_t)(bprefix[i] + rprefix[udiv(i, nbd)]);
     }
     __syncthreads();
+#endif
+    // (FDF_RANK_2PASS: the block prefixes stay row-relative and bitmap_rank adds the row's
+    // prefix, a word most lanes of a wave share.  u16 still holds them: a row-relative prefix is
+    // never larger than the absolute one, and the ranked tiers hold at most nms_area_entries
+    // keypoints)
     return *total;
 }
 
@@ -898,10 +1004,11 @@ __device__ uint32_t band_rank_prefixes(const uint32_t* bitmap, uint32_t R2, uint
 // again.
 template <bool RANKED>
 __device__ __forceinline__ uint32_t nms_entry(uint32_t e, const uint32_t* bitmap, uint32_t nw,
-                                              uint32_t nb_blocks, uint32_t y0, RowDiv W,
+                                              uint32_t nb_blocks, uint32_t y0, PosCode W,
                                               uint32_t H, uint32_t R2, const uint16_t* sranked,
                                               const uint16_t* bprefix, const uint32_t* rprefix) {
-    const uint32_t pos = e >> 12, row = udiv(pos, W), x = pos - row * W;
+    uint32_t row, x;
+    pos_decode(W, e >> 12, row, x);
     if (row == 0 || row == R2 - 1) return e;          // bitmap rows 0, R2-1: neighbours only
     const uint32_t y = y0 - 1 + row;
     const uint32_t low = e & 0xfffu;
@@ -939,10 +1046,11 @@ __device__ __forceinline__ uint32_t nms_entry(uint32_t e, const uint32_t* bitmap
 // at its raster rank; an isolated one is kept without comparison, marked by a zero score.
 template <bool RANKED = false>
 __device__ __forceinline__ uint32_t nms_scatter(uint32_t e, const uint32_t* bitmap, uint32_t nw,
-                                                uint32_t R2, uint32_t nb_blocks, RowDiv W,
+                                                uint32_t R2, uint32_t nb_blocks, PosCode W,
                                                 uint16_t* sranked, const uint16_t* bprefix,
                                                 const uint32_t* rprefix) {
-    const uint32_t pos = e >> 12, row = udiv(pos, W), x = pos - row * W;
+    uint32_t row, x;
+    pos_decode(W, e >> 12, row, x);
     if (neighbour_bits(bitmap, nw, R2, row, x) == 0) return e & ~0xfffu;
     const uint32_t rank = bitmap_rank(bitmap, bprefix, rprefix, nw, nb_blocks, row, x);
     sranked[rank] = (uint16_t)(e & 0xfffu);
@@ -950,9 +1058,10 @@ __device__ __forceinline__ uint32_t nms_scatter(uint32_t e, const uint32_t* bitm
     return e;
 }
 
-__device__ __forceinline__ void nms_clear(uint32_t e, uint32_t* bitmap, uint32_t nw, RowDiv W) {
+__device__ __forceinline__ void nms_clear(uint32_t e, uint32_t* bitmap, uint32_t nw, PosCode W) {
     if ((e & 0xfffu) == 1u) {
-        const uint32_t pos = e >> 12, row = udiv(pos, W), x = pos - row * W;
+        uint32_t row, x;
+        pos_decode(W, e >> 12, row, x);
         atomicAnd(&bitmap[row * nw + (x >> 5)], ~(1u << (x & 31)));
     }
 }
@@ -968,7 +1077,7 @@ __device__ __forceinline__ void nms_clear(uint32_t e, uint32_t* bitmap, uint32_t
 //   band's slot (`spill`); the LDS entries move to registers (kSpillPer per thread), so the
 //   ranked scores can use the whole FIFO + staging + list area.
 template <int NMS, int N>
-__device__ void band_nms_lds(uint32_t* bitmap, uint32_t rows, uint32_t nw, uint32_t y0, RowDiv W,
+__device__ void band_nms_lds(uint32_t* bitmap, uint32_t rows, uint32_t nw, uint32_t y0, PosCode W,
                              uint32_t H, uint32_t* slist, uint32_t n, uint16_t* sranked,
                              uint16_t* bprefix, uint32_t* rprefix, uint32_t* total, uint32_t flags) {
     const uint32_t tid = threadIdx.x;
@@ -990,7 +1099,7 @@ __device__ void band_nms_lds(uint32_t* bitmap, uint32_t rows, uint32_t nw, uint3
 constexpr uint32_t kSpillPer = kScoreListCap / kThreads;
 
 template <int NMS, int N>
-__device__ void band_nms_spill(uint32_t* bitmap, uint32_t rows, uint32_t nw, uint32_t y0, RowDiv W,
+__device__ void band_nms_spill(uint32_t* bitmap, uint32_t rows, uint32_t nw, uint32_t y0, PosCode W,
                                uint32_t H, const uint32_t* slist, uint32_t cap, uint32_t* spill,
                                uint32_t n, uint16_t* sranked, uint16_t* bprefix, uint32_t* rprefix,
                                uint32_t* total) {
@@ -1214,6 +1323,11 @@ __device__ __forceinline__ uint32_t sweep_band(const BandParams& P, uint8_t* sme
         return 0;
     }
     uint32_t* unit_ctr = wave_sum + kWaves;
+    static_assert(kThreads == 256, "one table entry per thread");
+#if FDF_SELTAB_CONST
+    // select_bit's table entry of byte tid, loaded before the bitmap clear that hides it
+    const uint32_t sel_word = kSelTab.v[tid];
+#endif
     // the bitmap and its pad word, cleared 16 bytes per store up to the (16-byte aligned)
     // end of its LDS area
     for (uint32_t i = tid; i < L.pq / 16; i += kThreads)
@@ -1222,8 +1336,10 @@ __device__ __forceinline__ uint32_t sweep_band(const BandParams& P, uint8_t* sme
         unit_ctr[0] = 0;
         unit_ctr[1] = 0;
     }
+#if FDF_SELTAB_CONST
+    reinterpret_cast<uint32_t*>(smem_raw + L.seltab)[tid] = sel_word;
+#else
     {   // select_bit's table: the positions of byte tid's set bits, the k-th in nibble k
-        static_assert(kThreads == 256, "one table entry per thread");
         uint32_t word = 0, k = 0;
 #pragma unroll
         for (uint32_t i = 0; i < 8; ++i) {
@@ -1233,6 +1349,7 @@ __device__ __forceinline__ uint32_t sweep_band(const BandParams& P, uint8_t* sme
         }
         reinterpret_cast<uint32_t*>(smem_raw + L.seltab)[tid] = word;
     }
+#endif
     if (P.chunk_flags && wave == 0) {
         // an overlapped upload (fdf_detect): wave 0 waits for the chunk holding the last row
         // the band reads -- its tested rows (with the NMS halo row) + 3 -- then acquires at
@@ -1265,8 +1382,9 @@ __device__ __forceinline__ uint32_t sweep_band(const BandParams& P, uint8_t* sme
     sh.bitmap = bitmap;
     sh.slist = reinterpret_cast<uint32_t*>(smem_raw + L.slist);
     sh.slist_n = unit_ctr + 1;
-    // list positions are (bitmap row * W + x) in 20 bits
-    sh.slist_cap = (uint64_t)(rows + 2 * halo) * W <= (1u << 20) ? kScoreListCap : 0u;
+    // list positions take 20 bits (PosCode)
+    sh.pc = make_poscode(W);
+    sh.slist_cap = pos_fits(sh.pc, rows + 2 * halo, W) ? kScoreListCap : 0u;
     sh.spill = reinterpret_cast<uint32_t*>(P.slots + (uint64_t)task * P.slot_bytes);
     sh.spill_cap = sh.slist_cap ? P.slot_bytes / 4 : 0u;
     sh.seltab = reinterpret_cast<const uint32_t*>(smem_raw + L.seltab);
@@ -1335,20 +1453,20 @@ __device__ __forceinline__ uint32_t sweep_band(const BandParams& P, uint8_t* sme
     __syncthreads();
 
     const uint32_t nwords = rows * nw;
-    const RowDiv Wd = make_rowdiv(W), nwd = make_rowdiv(nw);
+    const RowDiv nwd = make_rowdiv(nw);
     if constexpr (NMS != kNmsOff) {
         const uint32_t n = *sh.slist_n;
         if (tid == 0 && P.kp_stats) atomicAdd(P.kp_stats, n);
         if (ablation_flags(P.flags) & kFlagNoNms) {
         } else if (n <= sh.slist_cap) {
-            band_nms_lds<NMS, N>(bitmap, rows, nw, y0, Wd, H, sh.slist, n,
+            band_nms_lds<NMS, N>(bitmap, rows, nw, y0, sh.pc, H, sh.slist, n,
                                  reinterpret_cast<uint16_t*>(smem_raw + L.pq),
                                  reinterpret_cast<uint16_t*>(smem_raw + L.bprefix),
                                  reinterpret_cast<uint32_t*>(smem_raw + L.rprefix), unit_ctr + 2,
                                  ablation_flags(P.flags));
         } else if (n - sh.slist_cap <= sh.spill_cap && n <= L.nms_area_entries) {
             // more keypoints than the LDS list holds: the rest were appended to the slot
-            band_nms_spill<NMS, N>(bitmap, rows, nw, y0, Wd, H, sh.slist, sh.slist_cap, sh.spill, n,
+            band_nms_spill<NMS, N>(bitmap, rows, nw, y0, sh.pc, H, sh.slist, sh.slist_cap, sh.spill, n,
                                    reinterpret_cast<uint16_t*>(smem_raw + L.pq),
                                    reinterpret_cast<uint16_t*>(smem_raw + L.bprefix),
                                    reinterpret_cast<uint32_t*>(smem_raw + L.rprefix), unit_ctr + 2);
@@ -1378,6 +1496,25 @@ __device__ __forceinline__ uint32_t sweep_band(const BandParams& P, uint8_t* sme
     const uint32_t gq = (ngroups + kWaves - 1) / kWaves;
     const uint32_t gb = min(wave * gq, ngroups), ge = min(gb + gq, ngroups);
     uint32_t mine = 0;
+#if FDF_EMIT_REGS
+    // a wave's quarter of up to 64 * kEmitKeep groups (1080p: 353) stays in registers with
+    // its counts for the write pass; a larger one is read and counted again there.  Max-t
+    // instances only: it removes 1.9 M VALU per 1080p launch there, adds 0.4 M to a SAD launch
+    // and changes nothing without NMS.
+    constexpr uint32_t kEmitKeep = 6;
+    const bool in_regs = NMS == kNmsMaxThreshold && ge - gb <= 64 * kEmitKeep;   // wave-uniform
+    uint4 kq[kEmitKeep];
+    uint32_t kc[kEmitKeep];
+    if (in_regs) {
+#pragma unroll
+        for (uint32_t j = 0; j < kEmitKeep; ++j) {
+            const uint32_t g = gb + 64 * j + lane;
+            kq[j] = g < ge ? keep4[g] : make_uint4(0u, 0u, 0u, 0u);
+            kc[j] = __popc(kq[j].x) + __popc(kq[j].y) + __popc(kq[j].z) + __popc(kq[j].w);
+            mine += kc[j];
+        }
+    } else
+#endif
     for (uint32_t g = gb + lane; g < ge; g += 64) {
         const uint4 q = keep4[g];
         mine += __popc(q.x) + __popc(q.y) + __popc(q.z) + __popc(q.w);
@@ -1409,10 +1546,9 @@ __device__ __forceinline__ uint32_t sweep_band(const BandParams& P, uint8_t* sme
     if (listed || direct) {
         uint2* pts = reinterpret_cast<uint2*>(slot);
         uint32_t o = before;
-        for (uint32_t g0 = gb; g0 < ge; g0 += 64) {
+        // one round of 64 groups: group g0 + lane, its 4 words q and their keypoint count c
+        auto emit_round = [&](uint32_t g0, const uint4& q, uint32_t c) {
             const uint32_t g = g0 + lane;
-            const uint4 q = g < ge ? keep4[g] : make_uint4(0u, 0u, 0u, 0u);
-            const uint32_t c = __popc(q.x) + __popc(q.y) + __popc(q.z) + __popc(q.w);
             const uint32_t inc = wave_incl_scan(c);
             uint32_t idx = o + inc - c;
             o += __builtin_amdgcn_readlane(inc, 63);
@@ -1433,6 +1569,18 @@ __device__ __forceinline__ uint32_t sweep_band(const BandParams& P, uint8_t* sme
                 if (direct && dbase + idx < P.cap) P.out[dbase + idx] = pt;
                 ++idx;
             }
+        };
+#if FDF_EMIT_REGS
+        if (in_regs) {
+#pragma unroll
+            for (uint32_t j = 0; j < kEmitKeep; ++j)
+                if (gb + 64 * j < ge) emit_round(gb + 64 * j, kq[j], kc[j]);
+        } else
+#endif
+        for (uint32_t g0 = gb; g0 < ge; g0 += 64) {
+            const uint32_t g = g0 + lane;
+            const uint4 q = g < ge ? keep4[g] : make_uint4(0u, 0u, 0u, 0u);
+            emit_round(g0, q, __popc(q.x) + __popc(q.y) + __popc(q.z) + __popc(q.w));
         }
     }
     if (!listed) {
