@@ -3,7 +3,8 @@
 #   liboracle.so     scalar C restatement of the reference semantics (test infrastructure)
 #   libfast_avx2.so  C++ AVX2 port of the reference's fast_simd path (CPU baseline only)
 #   tests/cpp/test_cpp_*   smoke binaries of the C++ API (include/fdf.hpp): detection,
-#                          fdf::select_best, fdf::keypoint_angles, fdf::keypoint_descriptors,
+#                          fdf::select_best, fdf::keypoint_angles, fdf::keypoint_harris,
+#                          fdf::keypoint_descriptors,
 #                          fdf::match_descriptors, fdf::resize / fdf::build_pyramid
 #   tests/cpp/test_wg_share  host-only check of the kernels' work split (fdf_common.h)
 HIPCC ?= /opt/rocm/bin/hipcc
@@ -16,9 +17,9 @@ CSRC := $(PKG)/csrc
 LIBFDF := $(PKG)/libfdf.so
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Iinclude $(EXTRA_HIPFLAGS)
 OBJS := $(addprefix $(CSRC)/fdf_,$(addsuffix .o,kernels sweep sweep_latency sweep_rgb select \
-	orient describe match resize api stages pipeline))
+	orient harris describe match resize api stages pipeline))
 HEADERS := $(wildcard $(CSRC)/*.h) include/fdf.h
-CPP_TESTS := $(addprefix tests/cpp/test_cpp_,api select orient describe match pyramid)
+CPP_TESTS := $(addprefix tests/cpp/test_cpp_,api select orient harris describe match pyramid)
 
 all: $(LIBFDF) oracle/liboracle.so oracle/libfast_avx2.so $(CPP_TESTS) tests/cpp/test_wg_share
 

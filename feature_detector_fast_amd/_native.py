@@ -46,6 +46,7 @@ EXPORTED_SYMBOLS = (
     "fdf_describe_device", "fdf_describe_points", "fdf_match_device",
     "fdf_match_filter_device", "fdf_match_points", "fdf_resize_taps", "fdf_resize_device",
     "fdf_resize_frame", "fdf_pyramid_plan", "fdf_pyramid_taps", "fdf_pyramid_device",
+    "fdf_harris_codes", "fdf_harris_device", "fdf_harris_points",
 )
 
 
@@ -215,6 +216,13 @@ def load():
     lib.fdf_orient_device.argtypes = [vp, vp, u32, u32, u32, u64, vp, u64, vp, u32, vp, vp, vp]
     lib.fdf_orient_points.restype = ctypes.c_int
     lib.fdf_orient_points.argtypes = [vp, vp, u32, u32, sz, vp, sz, u32, vp, vp]
+    lib.fdf_harris_codes.restype = ctypes.c_int
+    lib.fdf_harris_codes.argtypes = [vp, sz, vp]
+    lib.fdf_harris_device.restype = ctypes.c_int
+    lib.fdf_harris_device.argtypes = [vp, vp, u32, u32, u32, u64, vp, u64, vp, u32, u32, u32, vp,
+                                      vp, vp]
+    lib.fdf_harris_points.restype = ctypes.c_int
+    lib.fdf_harris_points.argtypes = [vp, vp, u32, u32, sz, vp, sz, u32, u32, u32, vp, vp]
     lib.fdf_brief_pattern.restype = ctypes.c_int
     lib.fdf_brief_pattern.argtypes = [vp]
     lib.fdf_brief_steer.restype = ctypes.c_int

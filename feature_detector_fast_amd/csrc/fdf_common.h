@@ -1,5 +1,6 @@
 // fdf_common.h -- device helpers of every kernel file: a frame's index range, a workgroup's
-// share of it and raw buffer resources (fdf_select.hip, fdf_orient.hip, fdf_describe.hip);
+// share of it, raw buffer resources and the DPP sum of a keypoint's lanes (fdf_select.hip,
+// fdf_orient.hip, fdf_describe.hip, fdf_harris.hip);
 // circle geometry, byte-SWAR comparisons, wave ballots, the per-lane segment test and the two
 // NMS score functions of the reference (fdf_sweep.hip, fdf_kernels.hip).
 #pragma once
@@ -37,6 +38,23 @@ constexpr int kRawBufferWord3 = 0x00020000;
 template <typename T>
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t frame_rsrc(const T* base, int bytes) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(base), 0, bytes, kRawBufferWord3);
+}
+
+// v from the lane `ctrl` names (all rows and banks enabled)
+template <int CTRL>
+__device__ __forceinline__ int dpp(int v) {
+    return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, false);
+}
+
+// Sum over the L lanes of a keypoint (aligned groups of L), valid in every lane of the group
+// (fdf_orient.hip, fdf_harris.hip).
+template <int L>
+__device__ __forceinline__ int group_sum(int v) {
+    v += dpp<0xB1>(v);                            // quad_perm [1,0,3,2]
+    if constexpr (L >= 4) v += dpp<0x4E>(v);      // quad_perm [2,3,0,1]
+    if constexpr (L >= 8) v += dpp<0x141>(v);     // row_half_mirror: the other quad of 8
+    if constexpr (L >= 16) v += dpp<0x140>(v);    // row_mirror: the other half of 16
+    return v;
 }
 
 // ---------------------------------------------------------------------------------------

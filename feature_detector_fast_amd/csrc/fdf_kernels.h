@@ -1,5 +1,5 @@
 // fdf_kernels.h -- shared between the HIP kernels (fdf_sweep.hip, fdf_kernels.hip,
-// fdf_select.hip, fdf_orient.hip, fdf_describe.hip, fdf_match.hip) and the C-ABI host layer (fdf_api.cpp,
+// fdf_select.hip, fdf_orient.hip, fdf_harris.hip, fdf_describe.hip, fdf_match.hip) and the C-ABI host layer (fdf_api.cpp,
 // fdf_stages.cpp): geometry constants, LDS layout and launch parameters.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -286,7 +286,7 @@ hipError_t launch_select(const SelectParams& p, hipStream_t stream);
 constexpr int kOrientThreads = 256;
 constexpr uint32_t kOrientMaxRadius = 31;             // window of 2 r + 1 <= 64 bytes
 constexpr uint64_t kOrientMaxPixels = 0x7fffff00ull;  // byte offsets of a frame fit an int
-// launch_orient, launch_describe, launch_smooth: grid.y = n_frames, a frame an int can index
+// launch_orient, launch_harris, launch_describe, launch_smooth: grid.y = n_frames, a frame an int can index
 inline bool frames_fit_launch(uint32_t n_frames, uint32_t width, uint32_t height) {
     return n_frames <= 65535u && width != 0 && height != 0 &&
            (uint64_t)width * height <= kOrientMaxPixels;
@@ -304,6 +304,34 @@ struct OrientParams {
 };
 // one kernel on `stream`: `chunks` workgroups per frame share the frame's points
 hipError_t launch_orient(const OrientParams& p, uint32_t chunks, hipStream_t stream);
+
+// Harris corner response of keypoints (fdf_harris.hip; fdf_harris_device).
+constexpr int kHarrisThreads = 256;
+constexpr uint32_t kHarrisMaxK = 255;                 // k_num <= 255, 1 <= k_den <= 255
+inline bool harris_block_ok(uint32_t block) { return block == 3 || block == 5 || block == 7; }
+// The u16 rank score of a response: 0 for R <= 0, R itself below 1024, else a "6.10
+// minifloat" of e = floor(log2 R): (e - 9) << 10 | the 10 bits below R's leading one.
+// Monotone non-decreasing in R and continuous at 1023 -> 1024; 55295 at R = 2^63 - 1.
+__host__ __device__ inline uint16_t harris_code(int64_t R) {
+    if (R <= 0) return 0;
+    const int e = 63 - __builtin_clzll((unsigned long long)R);
+    if (e < 10) return (uint16_t)R;
+    return (uint16_t)(((uint32_t)(e - 9) << 10) | ((uint32_t)(R >> (e - 10)) & 1023u));
+}
+struct HarrisParams {
+    const uint8_t* frames;       // frame f at frames + f * frame_stride, width * height bytes
+    uint64_t frame_stride;
+    const uint2* pts;            // `cap` points, frames concatenated
+    const uint64_t* offs;        // n_frames + 1 entries
+    uint64_t cap;
+    uint32_t n_frames, width, height;
+    uint32_t block;              // 3, 5 or 7
+    uint32_t k_num, k_den;       // the Harris constant k_num / k_den
+    uint16_t* scores;            // `cap` rank scores
+    int64_t* responses;          // `cap` exact responses, or NULL
+};
+// one kernel on `stream`: `chunks` workgroups per frame share the frame's points
+hipError_t launch_harris(const HarrisParams& p, uint32_t chunks, hipStream_t stream);
 
 // Steered BRIEF descriptors and 5x5 box smoothing (fdf_describe.hip; fdf_describe_device,
 // fdf_smooth_device).

@@ -39,22 +39,6 @@ namespace fdfk {
 
 namespace {
 
-// v from the lane `ctrl` names (all rows and banks enabled)
-template <int CTRL>
-__device__ __forceinline__ int dpp(int v) {
-    return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, false);
-}
-
-// Sum over the L lanes of a keypoint (aligned groups of L), valid in every lane of the group.
-template <int L>
-__device__ __forceinline__ int group_sum(int v) {
-    v += dpp<0xB1>(v);                            // quad_perm [1,0,3,2]
-    if constexpr (L >= 4) v += dpp<0x4E>(v);      // quad_perm [2,3,0,1]
-    if constexpr (L >= 8) v += dpp<0x141>(v);     // row_half_mirror: the other quad of 8
-    if constexpr (L >= 16) v += dpp<0x140>(v);    // row_mirror: the other half of 16
-    return v;
-}
-
 // Byte mask of a lane's dword for a disc row of half-width u: the window bytes [r - u, r + u]
 // are in the disc and the lane holds the bytes [4j, 4j + 4); j8 = 32 j - 8 r, so both shift
 // counts, in bits, are one add and one clamp away.

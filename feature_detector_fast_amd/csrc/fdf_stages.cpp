@@ -1,5 +1,5 @@
 // fdf_stages.cpp -- the C ABI of the stages behind the detector (extensions: the reference
-// returns points only): best-K selection, orientation, steered BRIEF descriptors, box
+// returns points only): best-K selection, orientation, Harris response, steered BRIEF descriptors, box
 // smoothing, descriptor matching and the resize behind the scale pyramid.  Each has an asynchronous _device entry on the caller's stream and memory and a
 // host convenience _points entry.  Of a context they use the device, the mutex and the
 // stream only: its workspace and retained result (fdf_fetch_last) are not touched.
@@ -374,6 +374,95 @@ int fdf_orient_points(fdf_ctx* ctx, const uint8_t* data, uint32_t width, uint32_
                               out_moments ? a.at(d_mom) : nullptr, ctx->stream));
     a.download(out_angles, d_ang, n_points);
     if (out_moments) a.download(out_moments, d_mom, d_mom.count);
+    return a.close();
+}
+
+// ---- Harris corner response (fdf_harris.hip) ---------------------------------------------
+
+int fdf_harris_codes(const int64_t* responses, size_t n, uint16_t* codes) {
+    if (n && (!responses || !codes)) return FDF_ERR_ARG;
+    for (size_t k = 0; k < n; ++k) codes[k] = fdfk::harris_code(responses[k]);
+    return FDF_OK;
+}
+
+namespace {
+
+inline bool harris_args_ok(uint32_t block, uint32_t k_num, uint32_t k_den) {
+    return fdfk::harris_block_ok(block) && k_num <= fdfk::kHarrisMaxK && k_den >= 1 &&
+           k_den <= fdfk::kHarrisMaxK;
+}
+
+// The launch of fdf_harris_device / fdf_harris_points (arguments already validated).
+hipError_t harris_enqueue(const uint8_t* d_frames, uint32_t n_frames, uint32_t width,
+                          uint32_t height, uint64_t frame_stride, const fdf_point* d_points,
+                          uint64_t cap, const uint64_t* d_offsets, uint32_t block, uint32_t k_num,
+                          uint32_t k_den, uint16_t* d_scores, int64_t* d_responses,
+                          hipStream_t s) {
+    fdfk::HarrisParams p{};
+    p.frames = d_frames;
+    p.frame_stride = frame_stride;
+    p.pts = reinterpret_cast<const uint2*>(d_points);
+    p.offs = d_offsets;
+    p.cap = cap;
+    p.n_frames = n_frames;
+    p.width = width;
+    p.height = height;
+    p.block = block;
+    p.k_num = k_num;
+    p.k_den = k_den;
+    p.scores = d_scores;
+    p.responses = d_responses;
+    return fdfk::launch_harris(p, chunks_per_frame(cap, n_frames, width, height, 256, 256), s);
+}
+
+}  // namespace
+
+int fdf_harris_device(fdf_ctx* ctx, const uint8_t* d_frames, uint32_t n_frames, uint32_t width,
+                      uint32_t height, uint64_t frame_stride_bytes, const fdf_point* d_points,
+                      uint64_t cap, const uint64_t* d_frame_offsets, uint32_t block,
+                      uint32_t k_num, uint32_t k_den, uint16_t* d_scores, int64_t* d_responses,
+                      void* stream) {
+    if (!ctx || !d_frame_offsets || !harris_args_ok(block, k_num, k_den) || n_frames > 65535u ||
+        ((uintptr_t)d_responses & 7u) != 0)
+        return FDF_ERR_ARG;
+    uint64_t fs = 0;
+    bool todo = false;
+    const int rc = check_point_frames(n_frames, width, height, cap, frame_stride_bytes,
+                                      d_frames && d_points && d_scores, &fs, &todo);
+    if (!todo) return rc;
+    DeviceGuard guard(ctx->device);
+    return status_of(harris_enqueue(d_frames, n_frames, width, height, fs, d_points, cap,
+                                    d_frame_offsets, block, k_num, k_den, d_scores, d_responses,
+                                    reinterpret_cast<hipStream_t>(stream)));
+}
+
+int fdf_harris_points(fdf_ctx* ctx, const uint8_t* data, uint32_t width, uint32_t height,
+                      size_t stride_bytes, const fdf_point* points, size_t n_points,
+                      uint32_t block, uint32_t k_num, uint32_t k_den, uint16_t* out_scores,
+                      int64_t* out_responses) {
+    if (!ctx || !harris_args_ok(block, k_num, k_den)) return FDF_ERR_ARG;
+    if (n_points && (!points || !out_scores || !data)) return FDF_ERR_ARG;
+    if (stride_bytes < width) return FDF_ERR_ARG;
+    if (!points_inside(points, n_points, width, height)) return FDF_ERR_ARG;
+    if (n_points == 0) return FDF_OK;
+    const uint64_t frame_bytes = (uint64_t)width * height;
+    if (frame_bytes > fdfk::kOrientMaxPixels) return FDF_ERR_SIZE;
+    Arena a(ctx);
+    const auto d_frame = a.part<uint8_t>(frame_bytes);
+    const auto d_pts = a.part<fdf_point>(n_points);
+    const auto d_offs = a.part<uint64_t>(2);
+    const auto d_sc = a.part<uint16_t>(n_points);
+    const auto d_resp = a.part<int64_t>(out_responses ? n_points : 0);
+    if (a.open() != FDF_OK) return FDF_ERR_ALLOC;
+    a.upload_frame(d_frame, data, width, height, stride_bytes);
+    a.upload(d_pts, points);
+    a.upload_one_frame(d_offs, n_points);
+    if (a.ok())
+        a.note(harris_enqueue(a.at(d_frame), 1, width, height, frame_bytes, a.at(d_pts), n_points,
+                              a.at(d_offs), block, k_num, k_den, a.at(d_sc),
+                              out_responses ? a.at(d_resp) : nullptr, ctx->stream));
+    a.download(out_scores, d_sc, n_points);
+    if (out_responses) a.download(out_responses, d_resp, d_resp.count);
     return a.close();
 }
 

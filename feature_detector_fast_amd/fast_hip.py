@@ -796,6 +796,97 @@ def detect_oriented_array(img, config, radius=15, device=0):
     return pts, scores, keypoint_angles(arr, pts, r, device=device)
 
 
+def _harris_args(block, k):
+    """(block, k_num, k_den) of a Harris response: block 3, 5 or 7, k = (k_num, k_den) the
+    rational Harris constant with 0 <= k_num <= 255 and 1 <= k_den <= 255."""
+    b = int(block)
+    if b not in (3, 5, 7):
+        raise ValueError("block must be 3, 5 or 7")
+    try:
+        num, den = (int(v) for v in k)
+    except (TypeError, ValueError):
+        raise ValueError("k must be a pair of integers (k_num, k_den)") from None
+    if not (0 <= num <= 255 and 1 <= den <= 255):
+        raise ValueError("k = (k_num, k_den) needs 0 <= k_num <= 255 and 1 <= k_den <= 255")
+    return b, num, den
+
+
+def harris_codes(responses):
+    """The u16 rank scores of int64 Harris responses (fdf_harris_codes; host only, no device):
+    0 for R <= 0, R below 1024, else (e - 9) << 10 | the 10 bits below the leading one, with
+    e = floor(log2 R): monotone in R, the key select_device ranks by."""
+    r = np.asarray(responses)
+    if r.dtype != np.int64:
+        raise TypeError("responses must be an int64 array")
+    flat = np.ascontiguousarray(r).reshape(-1)
+    codes = np.zeros(flat.shape[0], dtype=np.uint16)
+    n = flat.shape[0]
+    check(_native.load().fdf_harris_codes(flat.ctypes.data if n else None, n,
+                                          codes.ctypes.data if n else None), "fdf_harris_codes")
+    return codes.reshape(r.shape)
+
+
+def harris_device(frames, points, offsets, scores, block=7, k=(1, 25), responses=None,
+                  stream=None, device=None):
+    """Harris corner responses of detect_device's (or select_device's) output, on the device
+    (fdf_harris_device): ``frames`` (F, H, W) uint8 with contiguous frames any number of bytes
+    apart, ``points`` (cap, 2) and ``offsets`` (F+1,) int64 as detect_device filled them.
+    ``scores`` (cap,) int16/uint16 gets the u16 rank score of every point's response over the
+    ``block`` x ``block`` (3, 5 or 7) Sobel gradients around it with the Harris constant
+    ``k`` = (k_num, k_den), ready for select_device; ``responses`` (optional, (cap,) int64) the
+    exact responses.  Asynchronous on ``stream`` (default: torch's current stream)."""
+    import torch
+
+    b, num, den = _harris_args(block, k)
+    _check_frames(torch, frames)
+    _check_points(points)
+    cap = points.shape[0]
+    if scores.dim() != 1 or scores.element_size() != 2 or scores.is_floating_point() or \
+            not scores.is_contiguous() or scores.numel() < cap:
+        raise ValueError("scores must be a contiguous 16-bit integer tensor with cap entries")
+    if responses is not None and (responses.dtype != torch.int64 or responses.dim() != 1 or
+                                  responses.numel() < cap or not responses.is_contiguous()):
+        raise ValueError("responses must be a contiguous int64 tensor with cap entries")
+    _check_offsets(torch, offsets, frames.shape[0] + 1)
+    _check_one_device("harris_device", [frames, points, offsets, scores] +
+                      ([responses] if responses is not None else []))
+    dev, stream = _device_stream(torch, frames, device, stream)
+    rc = _native.load().fdf_harris_device(
+        context(dev).handle, *_frame_args(frames),
+        points.data_ptr(), cap, offsets.data_ptr(), b, num, den, scores.data_ptr(),
+        responses.data_ptr() if responses is not None else None,
+        ctypes.c_void_p(stream.cuda_stream))
+    check(rc, "fdf_harris_device")
+
+
+def keypoint_harris(img, points, block=7, k=(1, 25), device=0, responses=False):
+    """Harris rank scores ((K,) uint16) of the given ``points`` (K, 2) of one image
+    (fdf_harris_points); with ``responses`` also the exact (K,) int64 responses.  Points
+    outside the image are an error."""
+    b, num, den = _harris_args(block, k)
+    arr = _as_pixels(img)
+    pts = _host_points(points)
+    h, w = arr.shape
+    n = pts.shape[0]
+    scores = np.zeros(n, dtype=np.uint16)
+    resp = np.zeros(n, dtype=np.int64) if responses else None
+    rc = _native.load().fdf_harris_points(
+        context(device).handle, arr.ctypes.data if arr.size else None, w, h,
+        arr.strides[0] if arr.size else w, pts.ctypes.data if n else None, n, b, num, den,
+        scores.ctypes.data if n else None, resp.ctypes.data if responses and n else None)
+    check(rc, "fdf_harris_points")
+    return (scores, resp) if responses else scores
+
+
+def detect_harris_array(img, config, block=7, k=(1, 25), device=0):
+    """detect_array followed by keypoint_harris: ((K, 2) uint32 points in raster order,
+    (K,) uint16 Harris rank scores), the pair select_best takes."""
+    b, num, den = _harris_args(block, k)
+    arr = _as_pixels(img)
+    pts = detect_array(arr, config, device=device)
+    return pts, keypoint_harris(arr, pts, b, (num, den), device=device)
+
+
 def _n_bins(n_bins):
     n = int(n_bins)
     if not 1 <= n <= 360:
@@ -1178,12 +1269,15 @@ MultiscaleKeypoints = collections.namedtuple(
 
 
 def detect_multiscale_array(img, config, n_levels=8, scale=(6, 5), cell=None, k=None, radius=15,
-                            n_bins=30, device=0):
+                            n_bins=30, device=0, rank="fast", block=7, harris_k=(1, 25)):
     """The keypoints of one host image over its scale pyramid: the image goes to the device
     once, the pyramid is built there (:class:`Pyramid`) and every level runs the device chain
     detect, score, (with ``cell`` = (cell_w, cell_h) and ``k``: best-k selection per cell,)
     orient on the level, describe on its 5 x 5 smoothed copy (default pattern, ``n_bins``
-    rotations).  Returns :class:`MultiscaleKeypoints`, ordered by level, then raster:
+    rotations).  ``rank`` = "fast" scores with the detector's score (score_device),
+    "harris" with the Harris rank score of the level (harris_device with ``block`` and the
+    Harris constant ``harris_k`` = (k_num, k_den); ``k`` is taken by the selection), ORB's
+    ranking: those scores feed the selection and are returned.  Returns :class:`MultiscaleKeypoints`, ordered by level, then raster:
     ``level`` (K,) int32, ``points`` (K, 2) uint32 level coordinates, ``points0`` (K, 2) float32
     level-0 coordinates ((x_l + 0.5) * w_0 / w_l - 0.5 per axis, in float64, rounded once),
     ``scores`` (K,) uint16, ``angles`` (K,) float32, ``descriptors`` (K, 32) uint8 and ``sizes``,
@@ -1196,6 +1290,9 @@ def detect_multiscale_array(img, config, n_levels=8, scale=(6, 5), cell=None, k=
     if cell is not None:
         cw, ch, k = _cell_k(cell, k)
         cell = (cw, ch)
+    if rank not in ("fast", "harris"):
+        raise ValueError('rank must be "fast" or "harris"')
+    hb, hnum, hden = _harris_args(block, harris_k)
     r = _radius(radius)
     bins = _n_bins(n_bins)
     arr = _as_pixels(img)
@@ -1227,7 +1324,10 @@ def detect_multiscale_array(img, config, n_levels=8, scale=(6, 5), cell=None, k=
                 continue
             pts = pts[:total]
             scores = torch.zeros(total, dtype=torch.int16, device=dev)
-            score_device(level, config, pts, offs, scores)
+            if rank == "harris":
+                harris_device(level, pts, offs, scores, hb, (hnum, hden))
+            else:
+                score_device(level, config, pts, offs, scores)
             if cell is not None:
                 sel = torch.zeros((total, 2), dtype=torch.int32, device=dev)
                 sel_scores = torch.zeros(total, dtype=torch.int16, device=dev)
@@ -1481,6 +1581,7 @@ __all__ = ["NORTH", "EAST", "SOUTH", "WEST", "circle", "calculate_offsets", "con
            "detect_scored_array", "detector_scored", "detector_batch_scored", "score_device",
            "select_scratch_bytes", "select_device", "select_best", "detect_best_array",
            "orient_disc", "orient_device", "keypoint_angles", "detect_oriented_array",
+           "harris_codes", "harris_device", "keypoint_harris", "detect_harris_array",
            "brief_pattern", "brief_steer", "smooth_device", "describe_device",
            "keypoint_descriptors", "detect_described_array",
            "resize_taps", "resize_device", "resize_array", "PyramidLevel", "PyramidPlan",

@@ -37,7 +37,7 @@ extern "C" {
  * fdf_brief_steer, fdf_smooth_device, fdf_describe_device and fdf_describe_points, and
  * fdf_match_device, fdf_match_filter_device and fdf_match_points, and fdf_resize_taps,
  * fdf_resize_device, fdf_resize_frame, fdf_pyramid_plan, fdf_pyramid_taps and
- * fdf_pyramid_device. */
+ * fdf_pyramid_device, and fdf_harris_codes, fdf_harris_device and fdf_harris_points. */
 #define FDF_ABI_VERSION 6
 
 /* Status codes.  Shapes the reference maps to an empty Vec return FDF_OK with 0 points. */
@@ -444,6 +444,73 @@ int fdf_orient_device(fdf_ctx* ctx, const uint8_t* d_frames, uint32_t n_frames, 
 int fdf_orient_points(fdf_ctx* ctx, const uint8_t* data, uint32_t width, uint32_t height,
                       size_t stride_bytes, const fdf_point* points, size_t n_points,
                       uint32_t radius, float* out_angles, int32_t* out_moments);
+
+/*
+ * Harris corner response of keypoints (extension: the reference returns points only; this is
+ * the score ORB ranks its FAST keypoints by, OpenCV's HarrisResponses / HARRIS_SCORE).
+ * Everything is exact integer arithmetic and a pure function of the inputs.
+ *
+ * Pixel reads.  I(cx, cy) is the pixel at (clamp(cx, 0, width - 1), clamp(cy, 0, height - 1)):
+ * the replicated border of fdf_orient_device.
+ *
+ * Gradients (3 x 3 Sobel), at any position (X, Y):
+ *   Ix = 2 (I(X+1,Y) - I(X-1,Y)) + (I(X+1,Y-1) - I(X-1,Y-1)) + (I(X+1,Y+1) - I(X-1,Y+1))
+ *   Iy = 2 (I(X,Y+1) - I(X,Y-1)) + (I(X-1,Y+1) - I(X-1,Y-1)) + (I(X+1,Y+1) - I(X+1,Y-1))
+ * so |Ix|, |Iy| <= 4 * 255 = 1020.
+ *
+ * Block sums.  block is 3, 5 or 7 (ORB's is 7), hb = block / 2.  For the keypoint (x, y), over
+ * |d| <= hb, |v| <= hb and (X, Y) = (x + d, y + v):
+ *   a = sum Ix^2,   b = sum Iy^2,   c = sum Ix Iy.
+ * a, b <= 49 * 1020^2 = 50 979 600 and |c| <= the same: all three fit int32.  The pixels read
+ * are the (block + 2)^2 window around the keypoint.
+ *
+ * Response.  R = k_den (a b - c^2) - k_num (a + b)^2 in int64; the Harris constant is the
+ * rational k = k_num / k_den, 0 <= k_num <= 255, 1 <= k_den <= 255 (ORB's 0.04 is 1 / 25).
+ * 0 <= a b - c^2 <= 50 979 600^2 and (a + b)^2 <= (2 * 50 979 600)^2 < 2^54, so both terms
+ * stay below 255 * (2 * 50 979 600)^2 < 2^62 < 2^63 and no step overflows.  For keypoints at
+ * least hb + 1 pixels inside the frame R / k_den * (1 / (4 * block * 255))^4 is OpenCV's float
+ * response up to its float rounding; no bit parity with OpenCV is claimed.
+ *
+ * Rank score (u16), the key fdf_select_device ranks by.  code(R) = 0 for R <= 0; otherwise with
+ * e = floor(log2 R): code = R for e < 10, and (e - 9) << 10 | ((R >> (e - 10)) & 1023) for
+ * e >= 10: a monotone non-decreasing "6.10 minifloat" of R (implicit leading bit, 10 mantissa
+ * bits), continuous at 1023 -> 1024, 55295 at R = 2^63 - 1.  Two responses get different
+ * codes whenever they differ in their top 11 significant bits; equal codes are broken by
+ * fdf_select_device's stable rule, and a caller who needs the exact order uses the int64 output.
+ *
+ * fdf_harris_codes: host only, no context; codes[i] = code(responses[i]).  FDF_ERR_ARG for a
+ * NULL pointer with n > 0.
+ *
+ * fdf_harris_device: the inputs are what fdf_detect_device (or fdf_select_device) leaves on
+ * the device: frame f owns the indices [offs[f], min(offs[f+1], cap)) and its pixels start at
+ * d_frames + f * frame_stride_bytes (any alignment).  d_scores gets `cap` rank scores,
+ * d_responses (optional, 8-byte aligned) `cap` int64 responses; entries at index
+ * >= min(offs[n_frames], cap) are not written.  Asynchronous on `stream` (NULL = the HIP null
+ * stream); like fdf_score_device it takes no context lock and uses no context workspace, it
+ * only binds the context's device; nothing is allocated and nothing returns to the host.
+ * FDF_ERR_ARG, synchronously and with nothing launched: a block other than 3, 5, 7, a k
+ * outside the ranges above, a NULL required pointer, n_frames > 65535, a frame stride below
+ * width * height when n_frames > 1, a d_responses that is not 8-byte aligned.  Shape errors
+ * and empty shapes as for fdf_score_device (FDF_OK, nothing written); width * height above
+ * 2^31 - 256 is FDF_ERR_SIZE.  A point with x >= width or y >= height gives an unspecified
+ * value for that point.  Whatever the points hold, no access leaves
+ * [d_frames, d_frames + (n_frames - 1) * stride + width * height) or the other buffers.
+ *
+ * fdf_harris_points: one host frame (rows stride_bytes apart) and host points, synchronous.
+ * Points outside the image are rejected with FDF_ERR_ARG.  Copies through device buffers
+ * allocated and freed by the call and runs the same kernel; the context's workspace and
+ * retained result are untouched, so fdf_fetch_last stays valid.  out_responses may be NULL.
+ */
+int fdf_harris_codes(const int64_t* responses, size_t n, uint16_t* codes);
+int fdf_harris_device(fdf_ctx* ctx, const uint8_t* d_frames, uint32_t n_frames, uint32_t width,
+                      uint32_t height, uint64_t frame_stride_bytes, const fdf_point* d_points,
+                      uint64_t cap, const uint64_t* d_frame_offsets, uint32_t block,
+                      uint32_t k_num, uint32_t k_den, uint16_t* d_scores, int64_t* d_responses,
+                      void* stream);
+int fdf_harris_points(fdf_ctx* ctx, const uint8_t* data, uint32_t width, uint32_t height,
+                      size_t stride_bytes, const fdf_point* points, size_t n_points,
+                      uint32_t block, uint32_t k_num, uint32_t k_den, uint16_t* out_scores,
+                      int64_t* out_responses);
 
 /*
  * Steered BRIEF descriptors (extension: the reference returns points only; this is the rBRIEF

@@ -16,6 +16,7 @@
 //   image::GrayImage                (image 0.24.6)       fdf::GrayView (borrowed row-major u8)
 //   (none: callers keep the best K)  --                   fdf::select_best(points, scores, ...)
 //   (none: ORB-style callers orient) --                   fdf::keypoint_angles(img, points, ...)
+//   (none: ... rank by Harris)       --                   fdf::keypoint_harris(img, points, ...)
 //   (none: ... and describe)         --                   fdf::keypoint_descriptors(img, points, ...)
 //   (none: ... and match)            --                   fdf::match_descriptors(q_desc, t_desc, ...)
 //   (none: ... over a scale pyramid) --                   fdf::resize, fdf::pyramid_plan, fdf::build_pyramid
@@ -240,6 +241,30 @@ inline std::vector<float> keypoint_angles(const GrayView& img, const std::vector
                                           uint32_t radius = 15,
                                           std::vector<int32_t>* moments = nullptr) {
     return keypoint_angles(img, points, radius, thread_context(), moments);
+}
+
+// Harris corner response (extension, fdf_harris_points): the u16 rank score of every point of
+// one image, from the `block` x `block` (3, 5 or 7; ORB's is 7) Sobel gradients around it and
+// the Harris constant k_num / k_den (ORB's 0.04 is 1 / 25); the pair select_best takes.
+// `responses` (optional) gets the exact int64 response per point.
+inline std::vector<uint16_t> keypoint_harris(const GrayView& img, const std::vector<Point>& points,
+                                             uint32_t block, uint32_t k_num, uint32_t k_den,
+                                             Context& ctx,
+                                             std::vector<int64_t>* responses = nullptr) {
+    std::vector<uint16_t> scores(points.size());
+    if (responses) responses->assign(points.size(), 0);
+    check(fdf_harris_points(ctx.get(), img.data, img.width, img.height, img.stride,
+                            reinterpret_cast<const fdf_point*>(points.data()), points.size(),
+                            block, k_num, k_den, scores.data(),
+                            responses ? responses->data() : nullptr),
+          "fdf_harris_points");
+    return scores;
+}
+inline std::vector<uint16_t> keypoint_harris(const GrayView& img, const std::vector<Point>& points,
+                                             uint32_t block = 7, uint32_t k_num = 1,
+                                             uint32_t k_den = 25,
+                                             std::vector<int64_t>* responses = nullptr) {
+    return keypoint_harris(img, points, block, k_num, k_den, thread_context(), responses);
 }
 
 // Steered BRIEF descriptors (extension, fdf_describe_points): 32 bytes per point of one image,
