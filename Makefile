@@ -5,7 +5,8 @@
 #   tests/cpp/test_cpp_*   smoke binaries of the C++ API (include/fdf.hpp): detection,
 #                          fdf::select_best, fdf::keypoint_angles, fdf::keypoint_harris,
 #                          fdf::keypoint_descriptors,
-#                          fdf::match_descriptors, fdf::resize / fdf::build_pyramid
+#                          fdf::match_descriptors, fdf::resize / fdf::build_pyramid,
+#                          fdf::estimate_model
 #   tests/cpp/test_wg_share  host-only check of the kernels' work split (fdf_common.h)
 HIPCC ?= /opt/rocm/bin/hipcc
 CC ?= gcc
@@ -17,9 +18,9 @@ CSRC := $(PKG)/csrc
 LIBFDF := $(PKG)/libfdf.so
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Iinclude $(EXTRA_HIPFLAGS)
 OBJS := $(addprefix $(CSRC)/fdf_,$(addsuffix .o,kernels sweep sweep_latency sweep_rgb select \
-	orient harris describe match resize api stages pipeline))
+	orient harris describe match ransac resize api stages pipeline))
 HEADERS := $(wildcard $(CSRC)/*.h) include/fdf.h
-CPP_TESTS := $(addprefix tests/cpp/test_cpp_,api select orient harris describe match pyramid)
+CPP_TESTS := $(addprefix tests/cpp/test_cpp_,api select orient harris describe match pyramid ransac)
 
 all: $(LIBFDF) oracle/liboracle.so oracle/libfast_avx2.so $(CPP_TESTS) tests/cpp/test_wg_share
 

@@ -46,7 +46,8 @@ EXPORTED_SYMBOLS = (
     "fdf_describe_device", "fdf_describe_points", "fdf_match_device",
     "fdf_match_filter_device", "fdf_match_points", "fdf_resize_taps", "fdf_resize_device",
     "fdf_resize_frame", "fdf_pyramid_plan", "fdf_pyramid_taps", "fdf_pyramid_device",
-    "fdf_harris_codes", "fdf_harris_device", "fdf_harris_points",
+    "fdf_harris_codes", "fdf_harris_device", "fdf_harris_points", "fdf_ransac_sample",
+    "fdf_ransac_scratch_bytes", "fdf_ransac_device", "fdf_ransac_points",
 )
 
 
@@ -71,8 +72,20 @@ class FdfPyramidLevel(ctypes.Structure):
                 ("xtaps_offset", ctypes.c_uint64), ("ytaps_offset", ctypes.c_uint64)]
 
 
+class FdfModel(ctypes.Structure):
+    """include/fdf.h fdf_model: 88 bytes."""
+    _fields_ = [("h", ctypes.c_double * 9), ("n_corr", ctypes.c_uint32),
+                ("n_inliers", ctypes.c_uint32), ("hypothesis", ctypes.c_uint32),
+                ("n_valid", ctypes.c_uint32)]
+
+
 FDF_MATCH_NONE = 0xFFFFFFFF
 FDF_MATCH_NO_DISTANCE = 0xFFFF
+FDF_COORDS_U32 = 0
+FDF_COORDS_F32 = 1
+FDF_MODEL_AFFINE = 0
+FDF_MODEL_HOMOGRAPHY = 1
+FDF_RANSAC_NONE = 0xFFFFFFFF
 
 
 class FdfError(RuntimeError):
@@ -255,6 +268,16 @@ def load():
     lib.fdf_pyramid_taps.argtypes = [levelp, u32, u32, u32, vp]
     lib.fdf_pyramid_device.restype = ctypes.c_int
     lib.fdf_pyramid_device.argtypes = [vp, vp, u32, u64, levelp, u32, vp, vp, vp]
+    lib.fdf_ransac_sample.restype = ctypes.c_int
+    lib.fdf_ransac_sample.argtypes = [u32, u32, u32, u32, u32, vp, ctypes.POINTER(u32)]
+    lib.fdf_ransac_scratch_bytes.restype = ctypes.c_int
+    lib.fdf_ransac_scratch_bytes.argtypes = [u32, u64, u32, ctypes.POINTER(u64)]
+    lib.fdf_ransac_device.restype = ctypes.c_int
+    lib.fdf_ransac_device.argtypes = [vp, u32, vp, vp, u64, vp, vp, vp, u64, vp, u32, u32, u32,
+                                      ctypes.c_float, u32, vp, vp, vp, u64, vp]
+    lib.fdf_ransac_points.restype = ctypes.c_int
+    lib.fdf_ransac_points.argtypes = [vp, vp, vp, sz, sz, vp, vp, u32, u32, u32, ctypes.c_float,
+                                      u32, vp, vp]
     del u8p
     _lib = lib
     return lib

@@ -1,5 +1,5 @@
 // fdf_kernels.h -- shared between the HIP kernels (fdf_sweep.hip, fdf_kernels.hip,
-// fdf_select.hip, fdf_orient.hip, fdf_harris.hip, fdf_describe.hip, fdf_match.hip) and the C-ABI host layer (fdf_api.cpp,
+// fdf_select.hip, fdf_orient.hip, fdf_harris.hip, fdf_describe.hip, fdf_match.hip, fdf_ransac.hip) and the C-ABI host layer (fdf_api.cpp,
 // fdf_stages.cpp): geometry constants, LDS layout and launch parameters.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -429,5 +429,78 @@ struct MatchFilterParams {
     uint8_t* keep;               // `q_cap` flags
 };
 hipError_t launch_match_filter(const MatchFilterParams& p, hipStream_t stream);
+
+// RANSAC affine / homography estimation from matches (fdf_ransac.hip; fdf_ransac_device).
+constexpr int kRansacThreads = 64;                    // hypotheses of a workgroup: one wave
+constexpr int kRansacFrameThreads = 256;              // compaction and finalisation: a workgroup per frame
+constexpr uint32_t kRansacTile = 256;                 // correspondences of an LDS tile (8 KB)
+constexpr int kRansacWideWaves = 8;                   // waves that share a block's scoring in a small grid
+constexpr uint32_t kRansacWideMaxBlocks = 128;        // ... one of at most this many blocks: 1024 waves
+constexpr uint32_t kRansacMaxHyp = 65536;
+constexpr uint32_t kRansacMaxDraws = 16;              // draws a sample may take
+constexpr uint32_t kRansacInvalid = 0xffffffffu;      // count of an invalid hypothesis; no best one
+constexpr uint32_t kRansacAffine = 0, kRansacHomography = 1;   // FDF_MODEL_*
+constexpr uint32_t kRansacU32 = 0, kRansacF32 = 1;             // FDF_COORDS_*
+
+// The sampling of include/fdf.h: the start state of (seed, frame, hypothesis) and the sample.
+__host__ __device__ inline uint32_t ransac_start_state(uint32_t seed, uint32_t frame, uint32_t hyp) {
+    uint32_t st = seed + 0x9E3779B9u * (frame + 1u) + 0x85EBCA6Bu * (hyp + 1u);
+    st ^= st >> 16;
+    st *= 0x85EBCA6Bu;
+    st ^= st >> 13;
+    st *= 0xC2B2AE35u;
+    st ^= st >> 16;
+    return st ? st : 0x9E3779B9u;
+}
+// The first S distinct draws in idx[0..S) and true, or kRansacInvalid in all of idx and false after
+// kRansacMaxDraws draws; *draws
+// (optional) gets the draws made.  Every index is a compile-time one: idx stays in registers.
+template <int S>
+__host__ __device__ inline bool ransac_sample(uint32_t seed, uint32_t frame, uint32_t hyp,
+                                              uint32_t m, uint32_t (&idx)[S], uint32_t* draws) {
+    uint32_t st = ransac_start_state(seed, frame, hyp);
+    int n = 0;
+    uint32_t d = 0;
+#pragma unroll
+    for (int k = 0; k < S; ++k) idx[k] = kRansacInvalid;
+    while (d < kRansacMaxDraws && n < S) {
+        st ^= st << 13;
+        st ^= st >> 17;
+        st ^= st << 5;
+        ++d;
+        const uint32_t j = (uint32_t)(((uint64_t)st * m) >> 32);
+        bool fresh = true;
+#pragma unroll
+        for (int k = 0; k < S; ++k) fresh = fresh && !(k < n && idx[k] == j);
+#pragma unroll
+        for (int k = 0; k < S; ++k) idx[k] = (fresh && k == n) ? j : idx[k];
+        n += fresh ? 1 : 0;
+    }
+    if (draws) *draws = d;
+#pragma unroll
+    for (int k = 0; k < S; ++k) idx[k] = n == S ? idx[k] : kRansacInvalid;
+    return n == S;
+}
+
+struct RansacParams {
+    const uint2* matches;        // `q_cap` fdf_match
+    const uint8_t* keep;         // `q_cap` flags, or NULL: all ones
+    const uint64_t* q_offs;      // n_frames + 1 entries
+    uint64_t q_cap;
+    const uint2* q_coords;       // `q_cap` points: 2 x u32 or 2 x f32 (the bits)
+    const uint2* t_coords;       // `t_cap` points
+    const uint64_t* t_offs;      // n_frames + 1 entries
+    uint64_t t_cap;
+    uint32_t n_frames, coords, model, n_hyp, seed;
+    double tt;                   // the threshold as a double, squared
+    double* models;              // n_frames fdf_model (11 x 8 bytes each)
+    uint8_t* inliers;            // `q_cap` flags, or NULL
+    double* corr;                // scratch: 4 doubles x, y, u, v per query index; frame f's
+                                 // correspondences packed from its first index on
+    uint32_t* n_corr;            // scratch: n_frames correspondence counts
+    uint32_t* counts;            // scratch: n_frames x n_hyp inlier counts (kRansacInvalid: none)
+};
+// compaction, hypothesis and finalisation kernels on `stream`
+hipError_t launch_ransac(const RansacParams& p, hipStream_t stream);
 
 }  // namespace fdfk

@@ -1,10 +1,11 @@
 // fdf_stages.cpp -- the C ABI of the stages behind the detector (extensions: the reference
 // returns points only): best-K selection, orientation, Harris response, steered BRIEF descriptors, box
-// smoothing, descriptor matching and the resize behind the scale pyramid.  Each has an asynchronous _device entry on the caller's stream and memory and a
+// smoothing, descriptor matching, RANSAC model estimation and the resize behind the scale pyramid.  Each has an asynchronous _device entry on the caller's stream and memory and a
 // host convenience _points entry.  Of a context they use the device, the mutex and the
 // stream only: its workspace and retained result (fdf_fetch_last) are not touched.
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 
 #include "fdf_ctx.h"
@@ -957,6 +958,146 @@ int fdf_match_points(fdf_ctx* ctx, const uint8_t* q_desc, const fdf_point* q_poi
                              a.at(d_t), window ? a.at(d_tp) : nullptr, n_t, a.at(d_to), max_dx,
                              max_dy, a.at(d_out), ctx->stream));
     a.download(out, d_out, n_q);
+    return a.close();
+}
+
+// ---- RANSAC affine / homography estimation (fdf_ransac.hip) --------------------------------
+namespace {
+
+static_assert(sizeof(fdf_model) == 88 && alignof(fdf_model) == 8 &&
+              offsetof(fdf_model, n_corr) == 72, "fdf_model is 9 doubles and 4 words");
+static_assert(FDF_COORDS_U32 == fdfk::kRansacU32 && FDF_COORDS_F32 == fdfk::kRansacF32 &&
+              FDF_MODEL_AFFINE == fdfk::kRansacAffine && FDF_MODEL_HOMOGRAPHY == fdfk::kRansacHomography &&
+              FDF_RANSAC_NONE == fdfk::kRansacInvalid, "the kernels' constants are the header's");
+
+// Scratch of one fdf_ransac_device call, every part 256-byte aligned: x, y, u, v per query
+// index, the correspondence count per frame, the inlier count per (frame, hypothesis).
+struct RansacLayout {
+    uint64_t corr = 0, n_corr = 0, counts = 0, total = 0;
+};
+
+int ransac_layout(uint32_t n_frames, uint64_t q_cap, uint32_t n_hyp, RansacLayout* L) {
+    if (n_frames > 65535u || q_cap > fdfk::kMatchMaxCap || n_hyp == 0 ||
+        n_hyp > fdfk::kRansacMaxHyp)
+        return FDF_ERR_ARG;
+    L->corr = 0;                                       // all below 2^38: no overflow
+    L->n_corr = L->corr + align256(4 * sizeof(double) * q_cap);
+    L->counts = L->n_corr + align256(sizeof(uint32_t) * n_frames);
+    L->total = L->counts + align256(sizeof(uint32_t) * (uint64_t)n_frames * n_hyp);
+    return FDF_OK;
+}
+
+// What fdf_ransac_device and fdf_ransac_points check of the values.
+inline bool ransac_values_ok(uint32_t coords, uint32_t model, float threshold) {
+    return coords <= FDF_COORDS_F32 && model <= FDF_MODEL_HOMOGRAPHY && std::isfinite(threshold) &&
+           threshold >= 0.0f;
+}
+
+}  // namespace
+
+int fdf_ransac_sample(uint32_t seed, uint32_t frame, uint32_t hypothesis, uint32_t m, uint32_t s,
+                      uint32_t idx[4], uint32_t* draws) {
+    if (!idx || (s != 3 && s != 4)) return FDF_ERR_ARG;
+    if (s == 3) {
+        uint32_t got[3];
+        fdfk::ransac_sample<3>(seed, frame, hypothesis, m, got, draws);
+        std::memcpy(idx, got, sizeof(got));
+        idx[3] = FDF_RANSAC_NONE;
+    } else {
+        uint32_t got[4];
+        fdfk::ransac_sample<4>(seed, frame, hypothesis, m, got, draws);
+        std::memcpy(idx, got, sizeof(got));
+    }
+    return FDF_OK;
+}
+
+int fdf_ransac_scratch_bytes(uint32_t n_frames, uint64_t q_cap, uint32_t n_hyp, uint64_t* bytes) {
+    if (!bytes) return FDF_ERR_ARG;
+    RansacLayout L;
+    const int rc = ransac_layout(n_frames, q_cap, n_hyp, &L);
+    if (rc) return rc;
+    *bytes = L.total;
+    return FDF_OK;
+}
+
+int fdf_ransac_device(fdf_ctx* ctx, uint32_t n_frames, const fdf_match* d_matches,
+                      const uint8_t* d_keep, uint64_t q_cap, const uint64_t* d_q_offsets,
+                      const void* d_q_coords, const void* d_t_coords, uint64_t t_cap,
+                      const uint64_t* d_t_offsets, uint32_t coords, uint32_t model,
+                      uint32_t n_hyp, float threshold, uint32_t seed, fdf_model* d_models,
+                      uint8_t* d_inliers, void* d_scratch, uint64_t scratch_bytes, void* stream) {
+    RansacLayout L;
+    if (!ctx || ransac_layout(n_frames, q_cap, n_hyp, &L) != FDF_OK ||
+        t_cap > fdfk::kMatchMaxCap || !ransac_values_ok(coords, model, threshold))
+        return FDF_ERR_ARG;
+    if (n_frames == 0) return FDF_OK;
+    if (!d_matches || !d_q_offsets || !d_t_offsets || !d_q_coords || !d_t_coords || !d_models ||
+        !d_scratch || scratch_bytes < L.total || ((uintptr_t)d_matches & 7u) != 0 ||
+        ((uintptr_t)d_q_coords & 7u) != 0 || ((uintptr_t)d_t_coords & 7u) != 0 ||
+        ((uintptr_t)d_models & 7u) != 0 || ((uintptr_t)d_scratch & 255u) != 0)
+        return FDF_ERR_ARG;
+    uint8_t* base = static_cast<uint8_t*>(d_scratch);
+    fdfk::RansacParams p{};
+    p.matches = reinterpret_cast<const uint2*>(d_matches);
+    p.keep = d_keep;
+    p.q_offs = d_q_offsets;
+    p.q_cap = q_cap;
+    p.q_coords = static_cast<const uint2*>(d_q_coords);
+    p.t_coords = static_cast<const uint2*>(d_t_coords);
+    p.t_offs = d_t_offsets;
+    p.t_cap = t_cap;
+    p.n_frames = n_frames;
+    p.coords = coords;
+    p.model = model;
+    p.n_hyp = n_hyp;
+    p.seed = seed;
+    p.tt = (double)threshold * (double)threshold;
+    p.models = reinterpret_cast<double*>(d_models);
+    p.inliers = d_inliers;
+    p.corr = reinterpret_cast<double*>(base + L.corr);
+    p.n_corr = reinterpret_cast<uint32_t*>(base + L.n_corr);
+    p.counts = reinterpret_cast<uint32_t*>(base + L.counts);
+    DeviceGuard guard(ctx->device);
+    return status_of(fdfk::launch_ransac(p, reinterpret_cast<hipStream_t>(stream)));
+}
+
+int fdf_ransac_points(fdf_ctx* ctx, const void* q_coords, const void* t_coords, size_t n_q,
+                      size_t n_t, const fdf_match* matches, const uint8_t* keep, uint32_t coords,
+                      uint32_t model, uint32_t n_hyp, float threshold, uint32_t seed,
+                      fdf_model* model_out, uint8_t* inliers_out) {
+    RansacLayout L;
+    if (!ctx || !model_out || ransac_layout(1, n_q, n_hyp, &L) != FDF_OK ||
+        n_t > fdfk::kMatchMaxCap || !ransac_values_ok(coords, model, threshold))
+        return FDF_ERR_ARG;
+    if (n_q && (!q_coords || !matches)) return FDF_ERR_ARG;
+    if (n_t && !t_coords) return FDF_ERR_ARG;
+    const uint64_t t_offs[2] = {0, n_t};                  // an asynchronous copy's source
+    Arena a(ctx);
+    const auto d_q = a.part<fdf_point>(n_q);
+    const auto d_t = a.part<fdf_point>(n_t);
+    const auto d_m = a.part<fdf_match>(n_q);
+    const auto d_keep = a.part<uint8_t>(keep ? n_q : 0);
+    const auto d_qo = a.part<uint64_t>(2);
+    const auto d_to = a.part<uint64_t>(2);
+    const auto d_model = a.part<fdf_model>(1);
+    const auto d_in = a.part<uint8_t>(inliers_out ? n_q : 0);
+    const auto d_scratch = a.part<uint8_t>(L.total);
+    if (a.open() != FDF_OK) return FDF_ERR_ALLOC;
+    if (n_q) a.upload(d_q, static_cast<const fdf_point*>(q_coords));
+    if (n_t) a.upload(d_t, static_cast<const fdf_point*>(t_coords));
+    if (n_q) a.upload(d_m, matches);
+    if (keep && n_q) a.upload(d_keep, keep);
+    a.upload_one_frame(d_qo, n_q);
+    a.upload(d_to, t_offs);
+    if (a.ok()) {
+        const int status = fdf_ransac_device(
+            ctx, 1, a.at(d_m), keep ? a.at(d_keep) : nullptr, n_q, a.at(d_qo), a.at(d_q),
+            a.at(d_t), n_t, a.at(d_to), coords, model, n_hyp, threshold, seed, a.at(d_model),
+            inliers_out ? a.at(d_in) : nullptr, a.at(d_scratch), L.total, ctx->stream);
+        if (status != FDF_OK) return status;
+    }
+    a.download(model_out, d_model, 1);
+    if (inliers_out && n_q) a.download(inliers_out, d_in, n_q);
     return a.close();
 }
 

@@ -1575,6 +1575,191 @@ def match_descriptors(q_desc, t_desc, q_points=None, t_points=None, window=None,
     return fwd, keep
 
 
+# include/fdf.h fdf_model as a numpy record; the (F, 11) float64 layout of ransac_device holds the
+# same 88 bytes per frame (unpack_models).
+MODEL_DTYPE = np.dtype([("h", "<f8", (9,)), ("n_corr", "<u4"), ("n_inliers", "<u4"),
+                        ("hypothesis", "<u4"), ("n_valid", "<u4")])
+RANSAC_NONE = _native.FDF_RANSAC_NONE
+_MODELS = {"affine": _native.FDF_MODEL_AFFINE, "homography": _native.FDF_MODEL_HOMOGRAPHY}
+_RANSAC_MAX_HYP = 65536
+
+
+def _ransac_model(model):
+    try:
+        return _MODELS[model]
+    except (KeyError, TypeError):
+        raise ValueError('model must be "affine" or "homography"') from None
+
+
+def _ransac_values(n_hyp, threshold, seed):
+    n_hyp, seed, threshold = int(n_hyp), int(seed), float(threshold)
+    if not 1 <= n_hyp <= _RANSAC_MAX_HYP:
+        raise ValueError("n_hyp must be in 1..65536")
+    if not (np.isfinite(ctypes.c_float(threshold).value) and threshold >= 0):   # as the C float
+        raise ValueError("threshold must be finite and not negative")
+    if not 0 <= seed <= 0xffffffff:
+        raise ValueError("seed must fit u32")
+    return n_hyp, threshold, seed
+
+
+def ransac_sample(seed, frame, hypothesis, m, s):
+    """The sample of one RANSAC hypothesis (fdf_ransac_sample): (the ``s`` correspondence numbers
+    below ``m`` or None when 16 draws do not give ``s`` distinct ones, the draws made)."""
+    idx = (ctypes.c_uint32 * 4)()
+    draws = ctypes.c_uint32()
+    for name, v in (("seed", seed), ("frame", frame), ("hypothesis", hypothesis), ("m", m)):
+        if not 0 <= int(v) <= 0xffffffff:
+            raise ValueError(f"{name} must fit u32")
+    if int(s) not in (3, 4):
+        raise ValueError("s must be 3 or 4")
+    check(_native.load().fdf_ransac_sample(int(seed), int(frame), int(hypothesis), int(m), int(s),
+                                           idx, ctypes.byref(draws)), "fdf_ransac_sample")
+    got = list(idx)[:int(s)]
+    return (None if got[0] == RANSAC_NONE else got), draws.value
+
+
+def ransac_scratch_bytes(n_frames, q_cap, n_hyp):
+    """Bytes of ransac_device's scratch tensor (fdf_ransac_scratch_bytes)."""
+    n_frames, q_cap, n_hyp = int(n_frames), int(q_cap), int(n_hyp)
+    if not (0 <= n_frames <= 65535 and 0 <= q_cap <= _MATCH_MAX_CAP):
+        raise ValueError("at most 65535 frames and fewer than 2^32 - 1 queries")
+    if not 1 <= n_hyp <= _RANSAC_MAX_HYP:
+        raise ValueError("n_hyp must be in 1..65536")
+    v = ctypes.c_uint64()
+    check(_native.load().fdf_ransac_scratch_bytes(n_frames, q_cap, n_hyp, ctypes.byref(v)),
+          "fdf_ransac_scratch_bytes")
+    return v.value
+
+
+def _check_coords(torch, t, name, rows, cap=0):
+    """FDF_COORDS_* of a (cap, 2) tensor of 32-bit integers or float32."""
+    if t.dim() != 2 or t.shape[1] != 2 or t.element_size() != 4 or not t.is_contiguous() or \
+            t.is_complex() or t.shape[0] < cap or t.shape[0] > _MATCH_MAX_CAP:
+        raise ValueError(f"{name} must be a contiguous ({rows}, 2) tensor of 32-bit integers or "
+                         "float32")
+    if t.data_ptr() % 8:
+        raise ValueError(f"{name} must be 8-byte aligned")
+    return _native.FDF_COORDS_F32 if t.is_floating_point() else _native.FDF_COORDS_U32
+
+
+def ransac_device(matches, q_offsets, q_coords, t_coords, t_offsets, models, scratch, keep=None,
+                  inliers=None, model="homography", n_hyp=256, threshold=3.0, seed=0,
+                  stream=None, device=None):
+    """RANSAC estimation of one affine map or homography per frame from match_device's output,
+    on the device (fdf_ransac_device).  ``matches`` (q_cap, 2) and ``q_offsets`` / ``t_offsets``
+    are match_device's, ``keep`` (optional) match_filter_device's; ``q_coords`` (q_cap, 2) and
+    ``t_coords`` (t_cap, 2) are both 32-bit integers (as detect_device fills them) or both
+    float32 (x, y).  ``models`` (F, 11) float64 gets one fdf_model per frame (unpack_models),
+    ``inliers`` (optional, (q_cap,) uint8) 1 for the inliers of each frame's best model.
+    ``scratch``: a uint8 tensor of ransac_scratch_bytes(F, q_cap, n_hyp), 256-byte aligned, no
+    initialisation needed.  The result is a pure function of the inputs and ``seed``.
+    Asynchronous on ``stream`` (default: torch's current stream)."""
+    import torch
+
+    _check_matches(matches, "matches", "q_cap")
+    q_cap = matches.shape[0]
+    n = _match_frames(torch, q_offsets, t_offsets)
+    kind = _check_coords(torch, q_coords, "q_coords", "q_cap", q_cap)
+    if _check_coords(torch, t_coords, "t_coords", "t_cap") != kind:
+        raise ValueError("q_coords and t_coords must have the same type")
+    t_cap = t_coords.shape[0]
+    if models.dtype != torch.float64 or models.dim() != 2 or models.shape[1] != 11 or \
+            models.shape[0] < n or not models.is_contiguous():
+        raise ValueError("models must be a contiguous (F, 11) float64 tensor")
+    for t, name in ((keep, "keep"), (inliers, "inliers")):
+        if t is not None and (t.dtype != torch.uint8 or t.dim() != 1 or t.numel() < q_cap or
+                              not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous uint8 tensor with q_cap entries")
+    code = _ransac_model(model)
+    n_hyp, threshold, seed = _ransac_values(n_hyp, threshold, seed)
+    if scratch.dtype != torch.uint8 or scratch.dim() != 1 or not scratch.is_contiguous() or \
+            scratch.numel() < ransac_scratch_bytes(n, q_cap, n_hyp):
+        raise ValueError("scratch must be a uint8 tensor of ransac_scratch_bytes(F, q_cap, n_hyp)")
+    if scratch.data_ptr() % 256:
+        raise ValueError("scratch must be 256-byte aligned")
+    _check_one_device("ransac_device",
+                      [matches, q_offsets, q_coords, t_coords, t_offsets, models, scratch] +
+                      [t for t in (keep, inliers) if t is not None])
+    dev, stream = _device_stream(torch, matches, device, stream)
+    rc = _native.load().fdf_ransac_device(
+        context(dev).handle, n, matches.data_ptr(), keep.data_ptr() if keep is not None else None,
+        q_cap, q_offsets.data_ptr(), q_coords.data_ptr(), t_coords.data_ptr(), t_cap,
+        t_offsets.data_ptr(), kind, code, n_hyp, threshold, seed, models.data_ptr(),
+        inliers.data_ptr() if inliers is not None else None, scratch.data_ptr(),
+        scratch.numel(), ctypes.c_void_p(stream.cuda_stream))
+    check(rc, "fdf_ransac_device")
+
+
+def unpack_models(array):
+    """(F,) records of MODEL_DTYPE from ransac_device's (F, 11) float64 array (a copy)."""
+    a = np.ascontiguousarray(array)
+    if a.dtype != np.float64 or a.ndim != 2 or a.shape[1] != 11:
+        raise TypeError("expected an (F, 11) float64 array")
+    return a.view(MODEL_DTYPE).reshape(-1).copy()
+
+
+def _host_coords(points, name):
+    """(contiguous (K, 2) uint32 or float32 array, FDF_COORDS_*)."""
+    pts = np.asarray(points)
+    if pts.ndim == 2 and pts.shape[1] == 2 and pts.dtype == np.float32:
+        return np.ascontiguousarray(pts), _native.FDF_COORDS_F32
+    if pts.ndim != 2 or pts.shape[1] != 2 or pts.dtype.kind not in "ui":
+        raise TypeError(f"{name} must be a (K, 2) integer or float32 array")
+    return _host_points(pts), _native.FDF_COORDS_U32
+
+
+def _host_matches(matches, n):
+    """(n,) MATCH_DTYPE records from records, the (n, 2) device layout, or (n,) train indices
+    (a negative one: no match)."""
+    a = np.asarray(matches)
+    if a.dtype == MATCH_DTYPE and a.ndim == 1:
+        rec = np.ascontiguousarray(a)
+    elif a.ndim == 2 and a.shape[1] == 2 and a.dtype.kind in "ui" and a.dtype.itemsize == 4:
+        rec = np.ascontiguousarray(a).view(MATCH_DTYPE).reshape(-1)
+    elif a.ndim == 1 and a.dtype.kind in "ui":
+        rec = np.zeros(len(a), dtype=MATCH_DTYPE)
+        index = a.astype(np.int64)
+        if index.size and index.max() > MATCH_NONE:
+            raise ValueError("match indices must fit u32")
+        rec["index"] = np.where(index < 0, MATCH_NONE, index)
+    else:
+        raise TypeError("matches must be match records, an (n, 2) 32-bit integer array or (n,) "
+                        "train indices")
+    if len(rec) != n:
+        raise ValueError("one match per query point")
+    return rec
+
+
+def estimate_model(q_points, t_points, matches, keep=None, model="homography", n_hyp=256,
+                   threshold=3.0, seed=0, device=0):
+    """RANSAC estimation of the affine map or homography that takes the query points to their
+    matches (fdf_ransac_points): (H as a (3, 3) float64 array or None when there is no model, the
+    (n_q,) bool inlier mask, the MODEL_DTYPE record).  ``q_points`` (n_q, 2) and ``t_points``
+    (n_t, 2) are both integer or both float32 arrays of (x, y); ``matches`` is match_descriptors'
+    result (or (n_q,) train indices, negative = none), ``keep`` an optional (n_q,) mask."""
+    q, kind = _host_coords(q_points, "q_points")
+    t, t_kind = _host_coords(t_points, "t_points")
+    if kind != t_kind:
+        raise TypeError("q_points and t_points must have the same type")
+    rec = _host_matches(matches, len(q))
+    if keep is not None:
+        keep = np.ascontiguousarray(np.asarray(keep) != 0, dtype=np.uint8)
+        if keep.shape != (len(q),):
+            raise ValueError("keep must have one entry per query point")
+    code = _ransac_model(model)
+    n_hyp, threshold, seed = _ransac_values(n_hyp, threshold, seed)
+    out = np.zeros(1, dtype=MODEL_DTYPE)
+    mask = np.zeros(len(q), dtype=np.uint8)
+    rc = _native.load().fdf_ransac_points(
+        context(device).handle, q.ctypes.data if len(q) else None,
+        t.ctypes.data if len(t) else None, len(q), len(t), rec.ctypes.data if len(q) else None,
+        keep.ctypes.data if keep is not None and len(q) else None, kind, code, n_hyp, threshold,
+        seed, out.ctypes.data, mask.ctypes.data if len(q) else None)
+    check(rc, "fdf_ransac_points")
+    found = out["hypothesis"][0] != RANSAC_NONE
+    return (out["h"][0].reshape(3, 3).copy() if found else None), mask.astype(bool), out[0]
+
+
 __all__ = ["NORTH", "EAST", "SOUTH", "WEST", "circle", "calculate_offsets", "context",
            "shard_contexts", "capacity_guess", "Lanes",
            "detect_array", "detector", "detector_batch", "detect_device", "keypoint_scores",
@@ -1589,6 +1774,8 @@ __all__ = ["NORTH", "EAST", "SOUTH", "WEST", "circle", "calculate_offsets", "con
            "detect_multiscale_array",
            "MATCH_DTYPE", "MATCH_NONE", "MATCH_NO_DISTANCE", "match_device",
            "match_filter_device", "unpack_matches", "match_descriptors",
+           "MODEL_DTYPE", "RANSAC_NONE", "ransac_sample", "ransac_scratch_bytes", "ransac_device",
+           "unpack_models", "estimate_model",
            "detect_rgb_array", "detector_rgb", "rgb_to_luma", "detect_device_rgb",
            "score_rings", "score_rings_device", "keypoint_score_max_threshold",
            "keypoint_score_sum_abs_difference", "NonMaximalSuppression"]

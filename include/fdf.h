@@ -37,7 +37,8 @@ extern "C" {
  * fdf_brief_steer, fdf_smooth_device, fdf_describe_device and fdf_describe_points, and
  * fdf_match_device, fdf_match_filter_device and fdf_match_points, and fdf_resize_taps,
  * fdf_resize_device, fdf_resize_frame, fdf_pyramid_plan, fdf_pyramid_taps and
- * fdf_pyramid_device, and fdf_harris_codes, fdf_harris_device and fdf_harris_points. */
+ * fdf_pyramid_device, and fdf_harris_codes, fdf_harris_device and fdf_harris_points, and
+ * fdf_ransac_sample, fdf_ransac_scratch_bytes, fdf_ransac_device and fdf_ransac_points. */
 #define FDF_ABI_VERSION 6
 
 /* Status codes.  Shapes the reference maps to an empty Vec return FDF_OK with 0 points. */
@@ -658,6 +659,118 @@ int fdf_match_filter_device(fdf_ctx* ctx, uint32_t n_frames, const fdf_match* d_
 int fdf_match_points(fdf_ctx* ctx, const uint8_t* q_desc, const fdf_point* q_points, size_t n_q,
                      const uint8_t* t_desc, const fdf_point* t_points, size_t n_t,
                      uint32_t max_dx, uint32_t max_dy, fdf_match* out);
+
+/*
+ * RANSAC estimation of an affine map or a homography from the matches (extension: the reference
+ * returns points only; the step after fdf_match_device / fdf_match_filter_device, OpenCV's
+ * estimateAffine2D / findHomography with RANSAC).  The result is a pure function of the inputs:
+ * the sampling is an integer generator, every floating-point step below is one IEEE binary64
+ * operation rounded once (never fused into a multiply-add), and ties are broken by index.
+ *
+ * Correspondences of frame f.  d_matches (q_cap entries), d_q_offsets and d_t_offsets are what
+ * fdf_match_device takes and leaves; d_keep (optional, q_cap bytes, NULL = all ones) is
+ * fdf_match_filter_device's; d_q_coords (q_cap) and d_t_coords (t_cap) hold 8 bytes per point:
+ * with coords = FDF_COORDS_U32 an fdf_point, as the detector and fdf_select_device write them,
+ * with FDF_COORDS_F32 two floats x, y (the level-0 coordinates of a multi-scale caller).  Both
+ * convert to double exactly.  Query i in [qo[f], min(qo[f+1], q_cap)) is a correspondence of
+ * frame f iff keep[i] != 0, matches[i].index != FDF_MATCH_NONE and matches[i].index lies in
+ * [to[f], min(to[f+1], t_cap)).  A frame's correspondences are numbered j = 0..M-1 in increasing
+ * i; correspondence j is (x, y) = the query coordinates of i and (u, v) = the train coordinates
+ * of matches[i].index.
+ *
+ * Model.  FDF_MODEL_AFFINE: sample size s = 3, N = 6 unknowns; FDF_MODEL_HOMOGRAPHY: s = 4,
+ * N = 8.  The result is nine doubles h0..h8, row-major, h8 = 1; affine: h6 = h7 = 0.
+ *
+ * Sampling of hypothesis h of frame f with the caller's seed, in uint32 with wrap:
+ *   st = seed + 0x9E3779B9 * (f + 1) + 0x85EBCA6B * (h + 1);
+ *   st ^= st >> 16; st *= 0x85EBCA6B; st ^= st >> 13; st *= 0xC2B2AE35; st ^= st >> 16;
+ *   if (st == 0) st = 0x9E3779B9;
+ * next() is fdf_brief_pattern's xorshift32 { st ^= st << 13; st ^= st >> 17; st ^= st << 5;
+ * return st; }.  A draw is j = ((uint64_t)next() * M) >> 32; it is accepted if it differs from
+ * the draws accepted before; the sample is the first s accepted draws in that order.  16 draws
+ * without s distinct values: the hypothesis is invalid (so is every hypothesis when M < s: the
+ * frame has no model).  The start state of seed 1, f 0, h 0 is 0xB0198235; (seed 1, f 0, h 0,
+ * M 100, s 4) gives 54, 11, 77, 18 after 4 draws, (1, 2, 7, 5, 4) gives 1, 0, 4, 2 after 5 and
+ * (0, 0, 0, 4, 4) gives 2, 1, 3, 0 after 7.
+ *
+ * Fit.  Sample point k = 0..s-1 gives two rows of the N x N system A h = b:
+ *   row 2k     = [x, y, 1, 0, 0, 0, -(u x), -(u y)],  b = u
+ *   row 2k + 1 = [0, 0, 0, x, y, 1, -(v x), -(v y)],  b = v
+ * (affine: the first six columns).  Gaussian elimination with partial pivoting, for column
+ * c = 0..N-1: the pivot row p is the lowest r >= c with the largest |A[r][c]| (a NaN magnitude
+ * never wins); the hypothesis is invalid unless |A[p][c]| >= 2^-20; rows c and p are swapped;
+ * for each r > c: m = A[r][c] / A[c][c], A[r][j] = A[r][j] - m * A[c][j] for j = c+1..N-1 and
+ * b[r] = b[r] - m * b[c].  Back substitution for i = N-1 down to 0: t = b[i]; for j = i+1..N-1
+ * ascending t = t - A[i][j] * h[j]; h[i] = t / A[i][i].
+ *
+ * Score.  For every correspondence of the frame, with T = (double)threshold:
+ *   P = (h0 x + h1 y) + h2,  Q = (h3 x + h4 y) + h5,  w = (h6 x + h7 y) + h8,
+ *   rx = P - u w,  ry = Q - v w,  e = rx rx + ry ry,  lim = (T T) (w w);
+ * an inlier iff w > 0 and e <= lim (both false for a NaN): a forward transfer error of at most
+ * T pixels, without a division.  A valid hypothesis' count is its number of inliers; the best
+ * hypothesis has the largest count, ties go to the lowest h.
+ *
+ * Output.  d_models[f] gets the best hypothesis' model bit for bit as fitted (no refit over the
+ * inliers), n_corr = M, n_inliers, hypothesis and n_valid = the number of valid hypotheses.  No
+ * valid hypothesis (or M < s): h all zero, n_inliers 0, hypothesis 0xFFFFFFFF.  d_inliers
+ * (optional, q_cap bytes) gets, for every i in [qo[0], min(qo[n_frames], q_cap)) and for no other
+ * byte, 1 if i is a correspondence and an inlier of its frame's best model and 0 otherwise.
+ *
+ * Example.  Queries (0,0), (10,0), (0,10), (10,10), (4,7), (20,3); trains = query + (3,5) except
+ * the fifth, (50,50); matches[i].index = i, seed 0, one frame, 8 hypotheses, T = 1.  Both models:
+ * hypothesis 3, 5 inliers, n_valid 8, inlier bytes 1 1 1 1 0 1, h = 1 0 3 0 1 5 0 0 1 (a zero
+ * may carry either sign).  The homography's counts per hypothesis are 1 2 1 5 2 1 2 2.
+ *
+ * fdf_ransac_sample: host only, no context; the sample of one hypothesis in idx[0..s) and the
+ * draws made in *draws (may be NULL).  An invalid hypothesis (m < s included) fills idx with
+ * 0xFFFFFFFF after its 16 draws.  FDF_ERR_ARG: s not 3 or 4, a NULL idx.
+ *
+ * fdf_ransac_scratch_bytes: host only; the size of fdf_ransac_device's d_scratch (256-byte
+ * aligned; needs no initialisation and may be reused in stream order): 32 bytes per query index,
+ * 4 per frame and 4 per (frame, hypothesis).  FDF_ERR_ARG: NULL bytes, n_frames > 65535,
+ * q_cap of 2^32 - 1 or more, n_hyp outside 1..65536.
+ *
+ * fdf_ransac_device: three kernels, asynchronous on `stream` (NULL = the HIP null stream); it
+ * takes no context lock and uses no context workspace, it only binds the context's device;
+ * nothing is allocated and nothing returns to the host.  FDF_ERR_ARG, synchronously and with
+ * nothing launched: n_frames > 65535, a cap of 2^32 - 1 or more, n_hyp outside 1..65536, a coords
+ * or model value that is none of the above, a threshold that is negative or not finite; and,
+ * unless n_frames == 0 (FDF_OK, nothing written): a NULL required pointer (all but d_keep and
+ * d_inliers), matches, coordinates or models that are not 8-byte aligned, a scratch that is not
+ * 256-byte aligned or too small.  Whatever the offsets, matches, keep bytes and coordinates hold,
+ * no access leaves the buffers; a match's index is checked against the frame's train range
+ * before the train coordinates are read.  Offsets that do not ascend give unspecified results.
+ *
+ * fdf_ransac_points: one pair of host sets (n_q queries with their matches and optional keep
+ * bytes, n_t train points), synchronous; inliers_out (n_q bytes) may be NULL.  Copies through
+ * device buffers allocated and freed by the call and runs the same kernels; the context's
+ * workspace and retained result are untouched, so fdf_fetch_last stays valid.
+ */
+#define FDF_COORDS_U32 0u   /* fdf_point */
+#define FDF_COORDS_F32 1u   /* float x, y */
+#define FDF_MODEL_AFFINE 0u
+#define FDF_MODEL_HOMOGRAPHY 1u
+#define FDF_RANSAC_NONE 0xFFFFFFFFu   /* hypothesis of a frame without a model; an idx of no sample */
+typedef struct fdf_model {
+    double h[9];           /* row-major 3 x 3, h[8] = 1; all zero without a model */
+    uint32_t n_corr;       /* M */
+    uint32_t n_inliers;
+    uint32_t hypothesis;   /* the best hypothesis, or FDF_RANSAC_NONE */
+    uint32_t n_valid;      /* valid hypotheses */
+} fdf_model;
+int fdf_ransac_sample(uint32_t seed, uint32_t frame, uint32_t hypothesis, uint32_t m, uint32_t s,
+                      uint32_t idx[4], uint32_t* draws);
+int fdf_ransac_scratch_bytes(uint32_t n_frames, uint64_t q_cap, uint32_t n_hyp, uint64_t* bytes);
+int fdf_ransac_device(fdf_ctx* ctx, uint32_t n_frames, const fdf_match* d_matches,
+                      const uint8_t* d_keep, uint64_t q_cap, const uint64_t* d_q_offsets,
+                      const void* d_q_coords, const void* d_t_coords, uint64_t t_cap,
+                      const uint64_t* d_t_offsets, uint32_t coords, uint32_t model,
+                      uint32_t n_hyp, float threshold, uint32_t seed, fdf_model* d_models,
+                      uint8_t* d_inliers, void* d_scratch, uint64_t scratch_bytes, void* stream);
+int fdf_ransac_points(fdf_ctx* ctx, const void* q_coords, const void* t_coords, size_t n_q,
+                      size_t n_t, const fdf_match* matches, const uint8_t* keep, uint32_t coords,
+                      uint32_t model, uint32_t n_hyp, float threshold, uint32_t seed,
+                      fdf_model* model_out, uint8_t* inliers_out);
 
 /*
  * Exact bilinear resize and the scale pyramid (extension: the reference detects at one scale;

@@ -19,6 +19,7 @@
 //   (none: ... rank by Harris)       --                   fdf::keypoint_harris(img, points, ...)
 //   (none: ... and describe)         --                   fdf::keypoint_descriptors(img, points, ...)
 //   (none: ... and match)            --                   fdf::match_descriptors(q_desc, t_desc, ...)
+//   (none: ... and fit a model)      --                   fdf::estimate_model(q_points, t_points, matches, ...)
 //   (none: ... over a scale pyramid) --                   fdf::resize, fdf::pyramid_plan, fdf::build_pyramid
 //
 // Where the reference panics (n < 9, n > 16, degenerate sizes) these throw fdf::Error.
@@ -331,6 +332,41 @@ inline std::vector<Match> match_descriptors(const std::vector<uint8_t>& q_desc,
                                             const std::vector<Point>* t_points = nullptr,
                                             uint32_t max_dx = 0, uint32_t max_dy = 0) {
     return match_descriptors(q_desc, t_desc, q_points, t_points, max_dx, max_dy, thread_context());
+}
+
+// RANSAC estimation of the affine map or homography that takes the query points to their
+// matches (extension, fdf_ransac_points; include/fdf.h has the sampling, fit and score rules:
+// the result is a pure function of the inputs and the seed).  `matches` holds one entry per query
+// point (match_descriptors' result), `keep` (optional) one flag per query.
+struct ModelEstimate {
+    fdf_model model;                  // h row-major; hypothesis == FDF_RANSAC_NONE: no model
+    std::vector<uint8_t> inliers;     // 1 for the queries that are inliers of the model
+    bool found() const { return model.hypothesis != FDF_RANSAC_NONE; }
+};
+inline ModelEstimate estimate_model(const std::vector<Point>& q_points,
+                                    const std::vector<Point>& t_points,
+                                    const std::vector<Match>& matches,
+                                    const std::vector<uint8_t>* keep, uint32_t model,
+                                    uint32_t n_hyp, float threshold, uint32_t seed, Context& ctx) {
+    if (matches.size() != q_points.size() || (keep && keep->size() != q_points.size()))
+        throw Error(FDF_ERR_ARG, "estimate_model: one match and keep flag per query point");
+    ModelEstimate out;
+    out.inliers.resize(q_points.size());
+    check(fdf_ransac_points(ctx.get(), q_points.data(), t_points.data(), q_points.size(),
+                            t_points.size(), matches.data(), keep ? keep->data() : nullptr,
+                            FDF_COORDS_U32, model, n_hyp, threshold, seed, &out.model,
+                            out.inliers.data()),
+          "fdf_ransac_points");
+    return out;
+}
+inline ModelEstimate estimate_model(const std::vector<Point>& q_points,
+                                    const std::vector<Point>& t_points,
+                                    const std::vector<Match>& matches,
+                                    const std::vector<uint8_t>* keep = nullptr,
+                                    uint32_t model = FDF_MODEL_HOMOGRAPHY, uint32_t n_hyp = 256,
+                                    float threshold = 3.0f, uint32_t seed = 0) {
+    return estimate_model(q_points, t_points, matches, keep, model, n_hyp, threshold, seed,
+                          thread_context());
 }
 
 // Exact bilinear resize and the scale pyramid (extension, fdf_resize_frame and
