@@ -135,7 +135,7 @@ Geometry pick_geometry(uint32_t n_frames, uint32_t w, uint32_t h, uint32_t nms,
                        uint64_t slots, double density, uint32_t forced_rows,
                        bool host_src = false) {
     Geometry g;
-    const uint32_t sc = (uint32_t)fdfk::strip_cols(fdfk::kLaneCols);
+    const uint32_t sc = (uint32_t)fdfk::kStripCols;
     g.nstrips = (w - 3 + sc - 1) / sc;
     // >= 4 units per band (one per wave), handed out dynamically; taller units (fewer halo
     // rows) measured faster than more, shorter units for balance

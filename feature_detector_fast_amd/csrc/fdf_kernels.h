@@ -44,32 +44,18 @@ constexpr uint32_t kStampWords = 12;
 // Column-sweep kernel (fdf_sweep.hip).  Lane l of a wave owns kLaneCols columns; a strip is
 // 62 lanes wide (lanes 0 and 63 are halo lanes).
 constexpr int kLaneCols = 16;
-__host__ __device__ constexpr int strip_cols(int lc) { return 62 * lc; }
+constexpr int kStripCols = 62 * kLaneCols;
 constexpr int kSweepPixelQ = 256;             // candidate pixel FIFO per wave (power of two)
 constexpr uint32_t kSweepMaxLds = 160 * 1024; // gfx950 LDS per CU (and per workgroup)
 
 // A full-test batch is issued every kSweepIssue rows once 64 candidates are queued and is
-// evaluated the same number of rows later.
-#ifndef FDF_ISSUE
-#define FDF_ISSUE 3
-#endif
-constexpr int kSweepIssue = FDF_ISSUE;
-// Full-test batches in flight (each evaluated kSweepBatchSlots issue points after its issue).
-#ifndef FDF_BATCH_SLOTS
-#define FDF_BATCH_SLOTS 1
-#endif
-constexpr int kSweepBatchSlots = FDF_BATCH_SLOTS;
+// evaluated the same number of rows later (one batch in flight per wave).
+constexpr int kSweepIssue = 3;
 // Pixel-row register ring of the sweep (rows in flight = kSweepRing - 4); unit sweeps are
 // whole multiples of kSweepRing steps.
-#ifndef FDF_RING
-#define FDF_RING 8
-#endif
-constexpr int kSweepRing = FDF_RING;
+constexpr int kSweepRing = 8;
 // Waves per SIMD of the sweep kernel (register budget 512 / kSweepWavesPerEU VGPRs).
-#ifndef FDF_WAVES_PER_EU
-#define FDF_WAVES_PER_EU 4
-#endif
-constexpr int kSweepWavesPerEU = FDF_WAVES_PER_EU;
+constexpr int kSweepWavesPerEU = 4;
 
 // Rows of keypoint bitmap above and below a band: NMS compares a band's edge rows with the
 // neighbouring bands' rows, so the band also tests one row each side (scores only).
@@ -82,10 +68,7 @@ __host__ __device__ inline uint32_t band_halo(uint32_t nms) { return nms ? 1u : 
 // per-4-word-block keypoint counts that turn a bitmap position into its raster rank.  The
 // FIFOs, staging and score list are contiguous: once the sweep is done they hold the scores
 // in rank order (`nms_area`, u16 entries; the FIFO part alone for band_nms_lds).
-#ifndef FDF_SLIST_CAP
-#define FDF_SLIST_CAP 2048
-#endif
-constexpr uint32_t kScoreListCap = FDF_SLIST_CAP;
+constexpr uint32_t kScoreListCap = 2048;
 constexpr uint32_t kRankBlock = 4;            // bitmap words per rank-prefix block
 // band_nms_lds ranks the list's scores as u16 into the 4 candidate FIFOs
 static_assert(kScoreListCap * 2 <= 4 * kSweepPixelQ * 4, "ranked scores must fit the FIFO area");
@@ -359,10 +342,7 @@ hipError_t launch_describe(const DescribeParams& p, uint32_t chunks, hipStream_t
 constexpr int kSmoothThreads = 256;
 constexpr uint32_t kSmoothMinWidth = 8;              // narrower frames: a thread per pixel
 // Rows a thread walks when the grid is large enough (4 halo rows are read per strip).
-#ifndef FDF_SMOOTH_STRIP
-#define FDF_SMOOTH_STRIP 64
-#endif
-constexpr uint32_t kSmoothStripRows = FDF_SMOOTH_STRIP;
+constexpr uint32_t kSmoothStripRows = 64;
 struct SmoothParams {
     const uint8_t* frames;       // frame f at frames + f * frame_stride, width * height bytes
     uint64_t frame_stride;

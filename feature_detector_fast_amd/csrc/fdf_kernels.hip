@@ -147,14 +147,14 @@ hipError_t launch_score_rings(const uint8_t* centers, const uint8_t* rings, uint
     const dim3 grid((nrings + 255) / 256), block(256);
     const uint4* r = reinterpret_cast<const uint4*>(rings);
     switch (n) {
-#define FDF_RING_CASE(NN)                                                                     \
+#define FDF_SCORE_CASE(NN)                                                                    \
     case NN:                                                                                 \
         hipLaunchKernelGGL(score_rings_kernel<NN>, grid, block, 0, stream, centers, r, nrings, \
                            nms, t, out);                                                     \
         break;
-        FDF_RING_CASE(9) FDF_RING_CASE(10) FDF_RING_CASE(11) FDF_RING_CASE(12)
-        FDF_RING_CASE(13) FDF_RING_CASE(14) FDF_RING_CASE(15) FDF_RING_CASE(16)
-#undef FDF_RING_CASE
+        FDF_SCORE_CASE(9) FDF_SCORE_CASE(10) FDF_SCORE_CASE(11) FDF_SCORE_CASE(12)
+        FDF_SCORE_CASE(13) FDF_SCORE_CASE(14) FDF_SCORE_CASE(15) FDF_SCORE_CASE(16)
+#undef FDF_SCORE_CASE
     }
     return hipGetLastError();
 }

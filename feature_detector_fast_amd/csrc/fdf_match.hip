@@ -27,9 +27,6 @@
 // Every train index read is below min(offs[f+1], t_cap), every query index below
 // min(offs[f+1], q_cap); writes go to the workgroup's own query range only.
 //
-// FDF_MATCH_SCALAR=1 builds the A/B alternative: no LDS, the wave-uniform
-// train descriptor is fetched into SGPRs by scalar loads.
-//
 // match_filter_kernel.  One thread per query index: the distance bound, the ratio test and
 // the cross-check of include/fdf.h; the index a match holds is compared with t_cap before the
 // reverse array is read at it.
@@ -39,20 +36,12 @@
 #include "fdf_common.h"
 #include "fdf_kernels.h"
 
-#ifndef FDF_MATCH_SCALAR
-#define FDF_MATCH_SCALAR 0
-#endif
-
 namespace fdfk {
 
 namespace {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef u32x4 __attribute__((aligned(4))) u32x4_a4;       // descriptors are 4-byte aligned
-typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
-typedef u32x8 __attribute__((aligned(4))) u32x8_a4;
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-#define FDF_CONSTANT __attribute__((address_space(4)))
 
 static_assert(kMatchTile == (uint32_t)kMatchThreads, "a thread fetches two pieces of a tile");
 
@@ -105,10 +94,8 @@ __device__ __forceinline__ uint32_t abs_diff(uint32_t a, uint32_t b) {
 
 template <bool WINDOW>
 __global__ __launch_bounds__(kMatchThreads) void match_kernel(MatchParams P) {
-#if !FDF_MATCH_SCALAR
     __shared__ u32x4 s_desc[2][2 * kMatchTile];
     __shared__ uint2 s_pts[2][WINDOW ? kMatchTile : 1];
-#endif
     __shared__ uint32_t s_y[2];
     const uint32_t f = blockIdx.y;
     const IndexRange qr = frame_range(P.q_offs, P.q_cap, f);
@@ -177,25 +164,6 @@ __global__ __launch_bounds__(kMatchThreads) void match_kernel(MatchParams P) {
         auto inside = [&](uint32_t tx, uint32_t ty) {
             return abs_diff(qp.x, tx) <= P.max_dx && abs_diff(qp.y, ty) <= P.max_dy;
         };
-#if FDF_MATCH_SCALAR
-        const FDF_CONSTANT uint8_t* t_desc = (const FDF_CONSTANT uint8_t*)P.t_desc;
-        const FDF_CONSTANT u32x2* t_pts = (const FDF_CONSTANT u32x2*)P.t_pts;
-        for (uint64_t j0 = jlo; j0 < jhi; j0 += kMatchTile) {
-            const uint32_t cnt = (uint32_t)min((uint64_t)kMatchTile, jhi - j0);
-            auto scan = [&](uint32_t k) {
-                const u32x8 t = *reinterpret_cast<const FDF_CONSTANT u32x8_a4*>(
-                    t_desc + (j0 + k) * kBriefBytes);
-                uint32_t d = hamming(q, u32x4{t[0], t[1], t[2], t[3]}, u32x4{t[4], t[5], t[6], t[7]});
-                if constexpr (WINDOW) {
-                    const u32x2 tp = t_pts[j0 + k];
-                    d = inside(tp.x, tp.y) ? d : kMatchNoDistance;
-                }
-                pair(d, k);
-            };
-            scan_tile(cnt, scan);
-            fold((uint32_t)j0);
-        }
-#else
         // this thread's two 16-byte pieces (and point) of the tile that starts at j0
         u32x4 stage[2] = {u32x4{0, 0, 0, 0}, u32x4{0, 0, 0, 0}};
         uint2 stage_pt = make_uint2(0u, 0u);
@@ -239,7 +207,6 @@ __global__ __launch_bounds__(kMatchThreads) void match_kernel(MatchParams P) {
             if (more) commit(buf ^ 1u);
             __syncthreads();
         }
-#endif
         if (live) P.matches[i] = make_uint2(idx, best | (second << 16));
     }
 }

@@ -1,6 +1,7 @@
 // fdf_sweep_impl.h -- column-sweep FAST-9..16 kernel for MI355X (gfx950), the production path.
 // Included by fdf_sweep.hip (grey frames: FDF_SWEEP_RGB 0, namespace fdfk::grey),
-// fdf_sweep_latency.hip (grey frames, units leave their last 8-step block early: namespace
+// fdf_sweep_latency.hip (grey frames, units leave their last 8-step block early and the emit
+// keeps nothing in registers, FDF_SWEEP_TU_EXIT 1 and FDF_SWEEP_TU_EMIT_REGS 0: namespace
 // fdfk::grey_lat) and fdf_sweep_rgb.hip (RGB8 frames converted to luma in the row and window
 // loads: FDF_SWEEP_RGB 1, namespace fdfk::rgb); each translation unit instantiates its 24
 // kernels.
@@ -13,7 +14,7 @@
 // and sweep them top to bottom:
 //   * lane l owns 16 columns (one 16-byte buffer load per row); lanes 0 and 63 are halo
 //     lanes that only feed their neighbours, so a strip covers 62 x 16 centres;
-//   * pixel rows stream through a register ring of kRing slots: kRing - 4 row loads
+//   * pixel rows stream through a register ring of kSweepRing slots: kSweepRing - 4 row loads
 //     are in flight, none is guarded by a branch and none is copied, so the compiler's vmcnt
 //     bookkeeping keeps them in flight;
 //   * every pairwise comparison is made once and used by both of its pixels: the vertical
@@ -52,36 +53,34 @@ namespace FDF_SWEEP_NS {
 
 // RGB8 input: 3 bytes per pixel, converted to luma as image 0.24.6 to_luma8 on load
 constexpr bool kRgb = FDF_SWEEP_RGB != 0;
-// The row ring and the occupancy target of this translation unit's kernels (kSweepRing /
-// kSweepWavesPerEU: 8 slots, 4 waves per SIMD, unless the unit overrides them).  A 16-slot
-// ring at 2 waves per SIMD for frames read in place over PCIe was measured slower (DESIGN.md
-// §7.5: PCIe read throughput, not latency, bounds that kernel).
-#ifndef FDF_SWEEP_TU_RING
-#define FDF_SWEEP_TU_RING kSweepRing
-#endif
-#ifndef FDF_SWEEP_TU_WAVES
-#define FDF_SWEEP_TU_WAVES kSweepWavesPerEU
-#endif
-constexpr int kRing = FDF_SWEEP_TU_RING;
-constexpr int kWavesEU = FDF_SWEEP_TU_WAVES;
-// Units that end inside an 8-step block leave it at their last row (FDF_SWEEP_TU_EXIT, the
-// latency instances of fdf_sweep_latency.hip: a single frame's 3-row units skip 4 padding
-// steps).  The exit tests perturb the long-unit loop's code (512 x 1080p max-t +0.5..+2 %,
-// DESIGN.md §7.6), so the throughput instances keep whole blocks.
+// Every unit's kernels use the row ring and the occupancy target of fdf_kernels.h (kSweepRing
+// = 8 slots, kSweepWavesPerEU = 4 waves per SIMD).  A 16-slot ring at 2 waves per SIMD for
+// frames read in place over PCIe was measured slower (PCIe read throughput,
+// not latency, bounds that kernel).
+//
+// The two per-unit parameters of this header:
+// FDF_SWEEP_TU_EXIT (default 0): units that end inside an 8-step block leave it at their last
+// row (the latency instances of fdf_sweep_latency.hip: a single frame's 3-row units skip 4
+// padding steps).  The exit tests perturb the long-unit loop's code (512 x 1080p max-t
+// +0.5..+2 %), so the throughput instances keep whole blocks.
 #ifndef FDF_SWEEP_TU_EXIT
 #define FDF_SWEEP_TU_EXIT 0
 #endif
 constexpr bool kExitInBlock = FDF_SWEEP_TU_EXIT != 0;
+// FDF_SWEEP_TU_EMIT_REGS (default 1): the max-t emit's write pass reuses the count pass's
+// bitmap groups from registers (sweep_band).  The latency unit sets it to 0:
+// its max-t kernels spill with it.
+#ifndef FDF_SWEEP_TU_EMIT_REGS
+#define FDF_SWEEP_TU_EMIT_REGS 1
+#endif
+constexpr bool kEmitRegs = FDF_SWEEP_TU_EMIT_REGS != 0;
 constexpr int kPx = kRgb ? 3 : 1;
 
+// A lane's kLaneCols = 16 bytes of one pixel row are one u32x4.
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
-
-// A lane's LC bytes of one pixel row (LC / 4 dwords).
-template <int LC> struct LaneRow;
-template <> struct LaneRow<16> { using type = u32x4; };
-template <> struct LaneRow<8> { using type = u32x2; };
+static_assert(kLaneCols == 16, "a lane row is four dwords; FIFO entries hold 16-bit lane masks");
 
 // DPP whole-wave shifts (GFX9 encodings): lane i reads lane i+1 / lane i-1.  The lane that
 // falls off the wave (63 / 0) is a halo lane whose results are never used, so its value is
@@ -101,7 +100,7 @@ struct RowSource {
     int tail_row;                // EXACT: rows >= tail_row may have windows crossing W * H
 };
 
-// Bytes [xb, xb+LC) of image row y: one LC-byte buffer load at any byte offset (gfx950
+// Bytes [xb, xb+16) of image row y: one 16-byte buffer load at any byte offset (gfx950
 // buffer loads need no alignment).  No branch, so the row prefetch stays a plain stream the
 // compiler's vmcnt bookkeeping can count.  Rows outside the frame and negative offsets read
 // 0; columns outside [0, W) hold neighbouring bytes (the next row, or up to 15 bytes past
@@ -133,19 +132,16 @@ __device__ __forceinline__ u32x4 luma16(const uint32_t (&d)[12]) {
     return r;
 }
 
-template <int LC, bool EXACT>
-__device__ __forceinline__ typename LaneRow<LC>::type load_row(const RowSource& src, int y,
-                                                              int xb) {
-    using RowV = typename LaneRow<LC>::type;
+template <bool EXACT>
+__device__ __forceinline__ u32x4 load_row(const RowSource& src, int y, int xb) {
     // y is wave-uniform, so the row test is scalar: a row outside [0, H) or past the unit's
     // last row gets an offset of 2^31 + xb, past any frame.  One VALU add per load; a
-    // negative xb in row 0 wraps to >= 2^32 - LC, also out of range (reads 0).  RGB frames:
+    // negative xb in row 0 wraps to >= 2^32 - 16, also out of range (reads 0).  RGB frames:
     // the same in bytes (3 per pixel).
     const bool in = y >= 0 && y < (int)src.H && y <= src.ylast;
     const uint32_t rowoff = in ? (uint32_t)(y * (int)src.W * kPx) : 0x80000000u;
     const int o = (int)(rowoff + (uint32_t)(xb * kPx));
     if constexpr (kRgb) {
-        static_assert(LC == 16, "RGB rows are loaded 16 pixels at a time");
         uint32_t d[12];
         if (EXACT && y >= src.tail_row) {   // wave-uniform
 #pragma unroll
@@ -165,23 +161,18 @@ __device__ __forceinline__ typename LaneRow<LC>::type load_row(const RowSource& 
     }
     if constexpr (EXACT) {
         if (y >= src.tail_row) {   // wave-uniform
-            RowV r = (RowV)(0u);
+            u32x4 r = (u32x4)(0u);
 #pragma unroll
-            for (int k = 0; k < LC; ++k)
+            for (int k = 0; k < kLaneCols; ++k)
                 r[k >> 2] |= (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(src.rs, o + k, 0, 0)
                              << (8 * (k & 3));
             return r;
         }
     }
-    if constexpr (LC == 16) {
-        // the row offset as the load's scalar offset and the lane's column as its vector
-        // offset (no per-lane add); a row off the frame takes the empty resource instead
-        (void)o;
-        return __builtin_bit_cast(RowV, __builtin_amdgcn_raw_buffer_load_b128(
-            in ? src.rs : src.none, xb, in ? y * (int)src.W : 0, 0));
-    }
-    else
-        return __builtin_bit_cast(RowV, __builtin_amdgcn_raw_buffer_load_b64(src.rs, o, 0, 0));
+    // the row offset as the load's scalar offset and the lane's column as its vector
+    // offset (no per-lane add); a row off the frame takes the empty resource instead
+    return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
+        in ? src.rs : src.none, xb, in ? y * (int)src.W : 0, 0));
 }
 
 // FIFO entries keep a lane row's 16 candidate flags and its code (row - ys) << 6 | lane in
@@ -198,80 +189,33 @@ __device__ __forceinline__ uint32_t pack_nibbles(uint32_t x) {
     return __builtin_amdgcn_perm(c, c, 0x0c0c0200u);
 }
 
-// Band-end switches, each on by default and separable for A/B builds
-// (tools/build_variant.sh NAME "-DFDF_POS_SHIFT=0" ...):
-//   FDF_POS_SHIFT     list positions are bitmap row << xbits | x instead of row * W + x
-//   FDF_RANK_2PASS    block rank prefixes stay row-relative (no third prefix pass)
-//   FDF_SELTAB_CONST  select_bit's table is a constant copied to LDS, not rebuilt per band
-//   FDF_EMIT_REGS     the max-t emit's write pass reuses the count pass's bitmap groups (the
-//                     latency unit, fdf_sweep_latency.hip, defaults it to 0: its kernels spill)
-#ifndef FDF_POS_SHIFT
-#define FDF_POS_SHIFT 1
-#endif
-#ifndef FDF_RANK_2PASS
-#define FDF_RANK_2PASS 1
-#endif
-#ifndef FDF_SELTAB_CONST
-#define FDF_SELTAB_CONST 1
-#endif
-#ifndef FDF_EMIT_REGS
-#define FDF_EMIT_REGS 1
-#endif
-
-// The 20 position bits of a score-list entry.  Shift-encoded: bitmap row << xbits | x with
-// xbits = ceil(log2 W) (per launch, wave-uniform), so the NMS passes get (row, x) back with a
-// shift and a mask where row * W + x needs a division.  Both forms are row-major, so raster
-// order -- all the rank scatter, the emit and the compaction rely on -- is the same.
-// A band's R2 = rows + 2 * halo bitmap rows fit when R2 <= 2^(20 - xbits).  2^xbits >= W, so
-// this is the stricter test of the two, but no geometry the automatic pick makes (LDS <=
-// 40 000 B, fdf_api.cpp) tells them apart: the bitmap alone takes R2 * nw * 4 bytes with
-// nw >= W / 32 > 2^(xbits - 6), so R2 < 40000 * 16 / 2^xbits < 2^20 / 2^xbits.  Only a band
-// height forced past that budget (fdf_ctx_set_band_rows, up to the 160 KB of a CU) can fit
-// row * W + x and not the shifted form; it then takes the dense tier, whose output is the
+// The 20 position bits of a score-list entry: bitmap row << xbits | x with xbits =
+// ceil(log2 W) (per launch, wave-uniform), so the NMS passes get (row, x) back with a shift
+// and a mask.  The code is row-major, so its order is raster order, which the rank scatter,
+// the emit and the compaction all rely on.
+// A band's R2 = rows + 2 * halo bitmap rows fit when R2 <= 2^(20 - xbits).  Every geometry the
+// automatic pick makes (LDS <= 40 000 B, fdf_api.cpp) fits: the bitmap alone takes R2 * nw * 4
+// bytes with nw >= W / 32 > 2^(xbits - 6), so R2 < 40000 * 16 / 2^xbits < 2^20 / 2^xbits.
+// Only a band height forced past that budget (fdf_ctx_set_band_rows, up to the 160 KB of a
+// CU) or a frame wider than 2^20 does not; it then takes the dense tier, whose output is the
 // same.
 struct PosCode {
-#if FDF_POS_SHIFT
     uint32_t xbits;
-#else
-    RowDiv W;
-#endif
 };
 __device__ __forceinline__ PosCode make_poscode(uint32_t W) {
     PosCode pc;
-#if FDF_POS_SHIFT
     pc.xbits = 32u - (uint32_t)__builtin_clz(W - 1u);   // W >= 7
-#else
-    pc.W = make_rowdiv(W);
-#endif
     return pc;
 }
-__device__ __forceinline__ bool pos_fits(const PosCode& pc, uint32_t R2, uint32_t W) {
-#if FDF_POS_SHIFT
-    (void)W;
+__device__ __forceinline__ bool pos_fits(const PosCode& pc, uint32_t R2) {
     return pc.xbits <= 20u && R2 <= (1u << (20u - pc.xbits));
-#else
-    (void)pc;
-    return (uint64_t)R2 * W <= (1u << 20);
-#endif
 }
-__device__ __forceinline__ uint32_t pos_encode(const PosCode& pc, uint32_t W, uint32_t row, uint32_t x) {
-#if FDF_POS_SHIFT
-    (void)W;
+__device__ __forceinline__ uint32_t pos_encode(const PosCode& pc, uint32_t row, uint32_t x) {
     return (row << pc.xbits) | x;
-#else
-    (void)pc;
-    // a full-rate 24-bit multiply
-    return mul_u24_s(W, row & 0x3ffu) + x;
-#endif
 }
 __device__ __forceinline__ void pos_decode(const PosCode& pc, uint32_t pos, uint32_t& row, uint32_t& x) {
-#if FDF_POS_SHIFT
     row = pos >> pc.xbits;
     x = pos & ((1u << pc.xbits) - 1u);
-#else
-    row = udiv(pos, pc.W);
-    x = pos - row * pc.W;
-#endif
 }
 
 struct SweepShared {
@@ -381,9 +325,9 @@ __device__ __forceinline__ uint32_t wave_max(uint32_t v) {
 }
 
 // Position of the j-th (from 0) set bit of a 16-bit mask that has more than j set bits.
-// seltab[b] holds the positions of byte b's set bits, the k-th in nibble k (in LDS, filled by
-// every workgroup before its sweep), so the mask needs one byte choice and one LDS read
-// instead of four halving steps.
+// seltab[b] holds the positions of byte b's set bits, the k-th in nibble k (in LDS, copied
+// there by every workgroup before its sweep), so the mask needs one byte choice and one LDS
+// read instead of four halving steps.
 struct SelTab {
     uint32_t v[256];
 };
@@ -398,10 +342,8 @@ constexpr SelTab make_seltab() {
     }
     return t;
 }
-#if FDF_SELTAB_CONST
 // the table in device memory (1 KB): a workgroup copies it to LDS with one load per thread
 __device__ const SelTab kSelTab = make_seltab();
-#endif
 __device__ __forceinline__ uint32_t select_bit(uint32_t m, uint32_t j, const uint32_t* seltab) {
     const uint32_t c8 = (uint32_t)__popc(m & 0xffu);
     const bool hi = j >= c8;
@@ -430,10 +372,8 @@ __device__ __forceinline__ FifoPeek fifo_peek(const SweepShared& sh, const UnitC
     return f;
 }
 
-template <int LC>
 __device__ __forceinline__ Batch issue_batch(const SweepShared& sh, UnitCtx& u, bool force,
                                              const FifoPeek& pk) {
-    static_assert(LC == 16, "16-bit lane masks");
     Batch b;
     b.n = 0;
     b.act = false;
@@ -489,7 +429,7 @@ __device__ __forceinline__ Batch issue_batch(const SweepShared& sh, UnitCtx& u, 
                 const uint32_t sc = scode;
                 b.code = ((uint32_t)(u.ys + (int)(sc >> 10)) << 10) | (sc & 1023u);
                 // rows relative to the unit (< 2^10) times W (< 2^16): a 24-bit multiply
-                o = u.rowbase + (int)__umul24(sc >> 10, (uint32_t)W) + u.S - LC + (int)(sc & 1023u);
+                o = u.rowbase + (int)__umul24(sc >> 10, (uint32_t)W) + u.S - kLaneCols + (int)(sc & 1023u);
             }
         }
     }
@@ -497,9 +437,8 @@ __device__ __forceinline__ Batch issue_batch(const SweepShared& sh, UnitCtx& u, 
     return b;
 }
 
-template <int LC>
 __device__ __forceinline__ Batch issue_batch(const SweepShared& sh, UnitCtx& u, bool force) {
-    return issue_batch<LC>(sh, u, force, fifo_peek(sh, u));
+    return issue_batch(sh, u, force, fifo_peek(sh, u));
 }
 
 __device__ __forceinline__ uint32_t perm(uint32_t hi, uint32_t lo, uint32_t sel) {
@@ -549,7 +488,7 @@ __device__ __forceinline__ void score_kp_queue(const SweepShared& sh, UnitCtx& u
                   (u.kq_c & 0xfffff000u) | score);
 }
 
-template <int NMS, int N, int LC>
+template <int NMS, int N>
 __device__ __forceinline__ void evaluate_batch(const SweepShared& sh, UnitCtx& u,
                                                const LerpConsts& lk, const Batch& b) {
     if (ablation_flags(u.flags) & kFlagNoEval) {   // ablation: consume the loads, test nothing
@@ -558,7 +497,7 @@ __device__ __forceinline__ void evaluate_batch(const SweepShared& sh, UnitCtx& u
         return;
     }
     const int y = (int)(b.code >> 10), cl = (int)(b.code & 1023u);
-    const int x = u.S - LC + cl;
+    const int x = u.S - kLaneCols + cl;
     uint32_t w[4], c;
     pack_ring(b, w, c);
     bool kb, kd;
@@ -579,7 +518,7 @@ __device__ __forceinline__ void evaluate_batch(const SweepShared& sh, UnitCtx& u
             if (is_kp) sh.stage[(q + lanes_below(bal)) & 63u] = u.lane;
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // see issue_batch
             const int src = (int)(sh.stage[u.lane] << 2);
-            const uint32_t pk = (pos_encode(sh.pc, u.src.W, (uint32_t)(y - u.yb), (uint32_t)x) << 12) |
+            const uint32_t pk = (pos_encode(sh.pc, (uint32_t)(y - u.yb), (uint32_t)x) << 12) |
                                 (kd ? 0x100u : 0u) | c;
             uint32_t nwv[4];
 #pragma unroll
@@ -613,7 +552,7 @@ __device__ __forceinline__ void evaluate_batch(const SweepShared& sh, UnitCtx& u
             if (is_kp) {
                 const uint32_t score = score_sum_abs_packed(c, w, u.t);
                 const uint32_t idx = base + lanes_below(bal);
-                const uint32_t e = (pos_encode(sh.pc, u.src.W, (uint32_t)(y - u.yb), (uint32_t)x) << 12) | score;
+                const uint32_t e = (pos_encode(sh.pc, (uint32_t)(y - u.yb), (uint32_t)x) << 12) | score;
                 if (idx < sh.slist_cap) sh.slist[idx] = e;
                 else if (idx - sh.slist_cap < sh.spill_cap) sh.spill[idx - sh.slist_cap] = e;
             }
@@ -621,49 +560,37 @@ __device__ __forceinline__ void evaluate_batch(const SweepShared& sh, UnitCtx& u
     }
 }
 
-// Horizontal/vertical comparison flags of one lane row (bit 7 of each byte, LC pixels).
-template <int LC>
+// Horizontal/vertical comparison flags of one lane row (bit 7 of each byte).
 struct RowFlags {
-    typename LaneRow<LC>::type b, nd;
+    u32x4 b, nd;
 };
 
 // Pre-filter comparisons of one lane row (bit 7 of each byte), exact (fdf_common.h).
-template <int LC>
-__device__ __forceinline__ RowFlags<LC> compare_rows(const typename LaneRow<LC>::type& x,
-                                                     const typename LaneRow<LC>::type& nc,
-                                                     const LerpConsts& k) {
-    RowFlags<LC> f;
+__device__ __forceinline__ RowFlags compare_rows(const u32x4& x, const u32x4& nc,
+                                                 const LerpConsts& k) {
+    RowFlags f;
 #pragma unroll
-    for (int m = 0; m < LC / 4; ++m) {
+    for (int m = 0; m < 4; ++m) {
         f.b[m] = lerp_u8(lerp_u8(x[m], nc[m], k.rb), k.kb, 0);   // x - c > t
         f.nd[m] = lerp_u8(lerp_u8(x[m], nc[m], k.rd), k.kd, 0);  // NOT(x - c < -t)
     }
     return f;
 }
 
-// Test everything queued, now (FIFO overflow, the end of a unit).
-template <int NMS, int N, int LC>
+// Test everything queued, now (the end of a unit): the batch in flight, then the FIFO.
+template <int NMS, int N>
 __device__ __forceinline__ void flush_tests(const SweepShared& sh, UnitCtx& u,
-                                            const LerpConsts& lk, bool (&inflight)[kSweepBatchSlots],
-                                            Batch (&batch)[kSweepBatchSlots]) {
-    constexpr int QL = kSweepBatchSlots - 1;
-#pragma unroll
-    for (int q = 0; q < QL; ++q) {
-        if (inflight[q]) {
-            evaluate_batch<NMS, N, LC>(sh, u, lk, batch[q]);
-            inflight[q] = false;
-        }
-    }
+                                            const LerpConsts& lk, bool& inflight, Batch& batch) {
     if (ablation_flags(u.flags) & kFlagNoFullTest) u.head = u.tail;
     // max-t measured 0.6-1.0% slower with the pipelined flush (its keypoint queue and score
     // keep more registers live), NMS off and SAD 0.2-1.5% faster (profiles/r02/ab_flush_rowdiv.txt)
     constexpr bool serial = NMS == kNmsMaxThreshold;
     if constexpr (serial) {
-        if (inflight[QL]) evaluate_batch<NMS, N, LC>(sh, u, lk, batch[QL]);
-        inflight[QL] = false;
+        if (inflight) evaluate_batch<NMS, N>(sh, u, lk, batch);
+        inflight = false;
         while (u.tail != u.head) {
-            const Batch b = issue_batch<LC>(sh, u, true);
-            evaluate_batch<NMS, N, LC>(sh, u, lk, b);
+            const Batch b = issue_batch(sh, u, true);
+            evaluate_batch<NMS, N>(sh, u, lk, b);
         }
         return;
     }
@@ -671,34 +598,32 @@ __device__ __forceinline__ void flush_tests(const SweepShared& sh, UnitCtx& u,
     // so a unit end with several queued batches waits for about one gather latency instead
     // of one per batch (the order keypoints are found in does not matter: bitmap bits, and
     // list entries ranked by position later).  Two batches alternate in fixed registers
-    // (A = the last slot, B), so no register with a load pending is ever copied.
-    Batch& A = batch[QL];
-    bool pa = inflight[QL];
+    // (A = the caller's, B), so no register with a load pending is ever copied.
+    Batch& A = batch;
+    bool pa = inflight;
     while (u.tail != u.head) {
-        const Batch B = issue_batch<LC>(sh, u, true);
-        if (pa) evaluate_batch<NMS, N, LC>(sh, u, lk, A);
+        const Batch B = issue_batch(sh, u, true);
+        if (pa) evaluate_batch<NMS, N>(sh, u, lk, A);
         pa = false;
         if (u.tail == u.head) {
-            evaluate_batch<NMS, N, LC>(sh, u, lk, B);
+            evaluate_batch<NMS, N>(sh, u, lk, B);
             break;
         }
-        A = issue_batch<LC>(sh, u, true);
+        A = issue_batch(sh, u, true);
         pa = true;
-        evaluate_batch<NMS, N, LC>(sh, u, lk, B);
+        evaluate_batch<NMS, N>(sh, u, lk, B);
     }
-    if (pa) evaluate_batch<NMS, N, LC>(sh, u, lk, A);
-    inflight[QL] = false;
+    if (pa) evaluate_batch<NMS, N>(sh, u, lk, A);
+    inflight = false;
 }
 
 template <int NMS, int N, bool EXACT>
 __device__ __forceinline__ void sweep_unit(const SweepShared& sh, UnitCtx& u, const LerpConsts& lk) {
-    constexpr int LC = kLaneCols;
-    constexpr int M = LC / 4;
+    constexpr int M = kLaneCols / 4;                   // dwords of a lane row
     constexpr int kIssue = kSweepIssue;
-    using RowV = typename LaneRow<LC>::type;
     const uint32_t lane = u.lane;
     const int W = (int)u.src.W;
-    const int xb = u.S - LC + LC * (int)lane;
+    const int xb = u.S - kLaneCols + kLaneCols * (int)lane;
     // candidate columns of this lane: the strip's centres (halo lanes 0 and 63 own none)
     // (bit 8j + 4 + m = lane column 4m + j, the order the FIFO entry's flags are built in)
     uint32_t vmask = 0;
@@ -718,53 +643,50 @@ __device__ __forceinline__ void sweep_unit(const SweepShared& sh, UnitCtx& u, co
     const int T = p1 - ys;                             // sweep steps (row ys + i at step i)
     u.src.ylast = p1 + 2;                              // S-row of the last pre-filtered row
     u.head = u.tail = 0;
-    // kSweepBatchSlots batches in flight, in static slots (issue point q of the K-step loop
-    // body uses slot q % slots), each evaluated slots issue points after it was issued
-    bool inflight[kSweepBatchSlots];
-    Batch batch[kSweepBatchSlots];
-#pragma unroll
-    for (int q = 0; q < kSweepBatchSlots; ++q) inflight[q] = false;
+    // one batch in flight: issued at an issue point of the loop body, evaluated at the next
+    bool inflight = false;
+    Batch batch;
 
-    // One kRing-slot ring of pixel rows: row r in slot (r - ys) % kRing.  At step J
-    // (row yv) it holds rows yv .. yv+K-2 (K = kRing) with yv+4 .. yv+K-2 still loading,
+    // One K-slot ring of pixel rows (K = kSweepRing): row r in slot (r - ys) % K.  At step J
+    // (row yv) it holds rows yv .. yv+K-2 with yv+4 .. yv+K-2 still loading,
     // and row yv+K-1 is loaded into the slot of row yv-1, which is dead.  Nothing is copied,
     // so every slot keeps its registers across loop iterations and no wait is needed for a
     // register move.  The loop body is K steps, so unit sweeps are whole multiples of K.
-    constexpr int K = kRing;
-    RowV Rw[K];
+    constexpr int K = kSweepRing;
+    u32x4 Rw[K];
     // The N flags of rows p0 .. p0+2 come from the vertical comparisons of rows p0-3 .. p0-1
     // with them, which the steps of those rows would have made: a prologue makes only those
     // three comparisons (3 loads and 48 lerps instead of three whole pre-filter steps whose
     // candidates are masked)
-    RowV up[3];
+    u32x4 up[3];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) up[k] = load_row<LC, EXACT>(u.src, ys - 3 + k, xb);
+    for (int k = 0; k < 3; ++k) up[k] = load_row<EXACT>(u.src, ys - 3 + k, xb);
 #pragma unroll
-    for (int k = 0; k < K - 1; ++k) Rw[k] = load_row<LC, EXACT>(u.src, ys + k, xb);
-    RowFlags<LC> V[4];                                 // vertical flags, slot (row-ys) & 3
+    for (int k = 0; k < K - 1; ++k) Rw[k] = load_row<EXACT>(u.src, ys + k, xb);
+    RowFlags V[4];                                     // vertical flags, slot (row-ys) & 3
 #pragma unroll
-    for (int k = 0; k < 3; ++k) V[k + 1] = compare_rows<LC>(Rw[k], ~up[k], lk);
+    for (int k = 0; k < 3; ++k) V[k + 1] = compare_rows(Rw[k], ~up[k], lk);
     // Step J: next row load, comparisons, pre-filter of row yv, enqueue of its candidates.
     // Rows outside [p0, p1) (look-ahead and padding steps) run the pre-filter too and have
     // their candidates masked: a branch around it costs the zeroing of `cand` on every step.
 #define FDF_SWEEP_STEP(J)                                                                    \
     {                                                                                        \
         const int yv = ys + i0 + (J);                                                        \
-        RowV cand = (RowV)(0u);                                                              \
-        Rw[((J) + K - 1) % K] = load_row<LC, EXACT>(u.src, yv + K - 1, xb);                  \
-        const RowV s = Rw[((J) + 3) % K];                  /* row yv + 3 */                  \
-        const RowV c = Rw[(J) % K];                        /* row yv */                      \
-        const RowV nc = ~c;                                                                  \
-        V[(J) & 3] = compare_rows<LC>(s, nc, lk);                                            \
-        const bool live = yv >= p0 && yv < p1 && !(ablation_flags(u.flags) & kFlagNoLoad);                  \
+        u32x4 cand = (u32x4)(0u);                                                            \
+        Rw[((J) + K - 1) % K] = load_row<EXACT>(u.src, yv + K - 1, xb);                      \
+        const u32x4 s = Rw[((J) + 3) % K];                 /* row yv + 3 */                  \
+        const u32x4 c = Rw[(J) % K];                       /* row yv */                      \
+        const u32x4 nc = ~c;                                                                 \
+        V[(J) & 3] = compare_rows(s, nc, lk);                                                \
+        const bool live = yv >= p0 && yv < p1 && !(ablation_flags(u.flags) & kFlagNoLoad);   \
         {                                                                                    \
-            RowV e;                                                                          \
+            u32x4 e;                                                                         \
             _Pragma("unroll") for (int m = 0; m + 1 < M; ++m) e[m] = alignbyte(c[m + 1], c[m], 3); \
             e[M - 1] = alignbyte(from_next_lane(c[0]), c[M - 1], 3);                         \
-            const RowFlags<LC> h = compare_rows<LC>(e, nc, lk);                              \
+            const RowFlags h = compare_rows(e, nc, lk);                                      \
             const uint32_t pb = from_prev_lane(h.b[M - 1]), pnd = from_prev_lane(h.nd[M - 1]); \
-            const RowFlags<LC>& vs = V[(J) & 3];                                             \
-            const RowFlags<LC>& vn = V[((J) + 1) & 3];                                       \
+            const RowFlags& vs = V[(J) & 3];                                                 \
+            const RowFlags& vn = V[((J) + 1) & 3];                                           \
             _Pragma("unroll") for (int m = 0; m < M; ++m) {                                  \
                 const uint32_t hbw = alignbyte(h.b[m], m ? h.b[m - 1] : pb, 1);              \
                 const uint32_t hndw = alignbyte(h.nd[m], m ? h.nd[m - 1] : pnd, 1);          \
@@ -814,26 +736,23 @@ __device__ __forceinline__ void sweep_unit(const SweepShared& sh, UnitCtx& u, co
             u.tail += (uint32_t)__popcll(bal);                                               \
             while (u.tail - u.head > kSweepPixelQ - 64) {                                    \
                 /* dense image: test the oldest pixels now, synchronously */                 \
-                if (ablation_flags(u.flags) & kFlagNoFullTest) u.head = u.tail;                              \
-                else evaluate_batch<NMS, N, LC>(sh, u, lk, issue_batch<LC>(sh, u, true));    \
+                if (ablation_flags(u.flags) & kFlagNoFullTest) u.head = u.tail;              \
+                else evaluate_batch<NMS, N>(sh, u, lk, issue_batch(sh, u, true));            \
             }                                                                                \
         }                                                                                    \
         if (((J) % kIssue) == kIssue - 1) {                                                  \
-            /* the batch of this slot is due; issue the next full one into it */             \
-            constexpr int q = ((J) / kIssue) % kSweepBatchSlots;                             \
-            if (inflight[q]) {                                                               \
-                evaluate_batch<NMS, N, LC>(sh, u, lk, batch[q]);                             \
-                inflight[q] = false;                                                         \
+            /* the batch in flight is due; issue the next full one in its place */           \
+            if (inflight) {                                                                  \
+                evaluate_batch<NMS, N>(sh, u, lk, batch);                                    \
+                inflight = false;                                                            \
             }                                                                                \
-            if (ablation_flags(u.flags) & kFlagNoFullTest) u.head = u.tail;                                  \
-            batch[q] = issue_batch<LC>(sh, u, false);                                        \
-            inflight[q] = batch[q].n != 0;                                                   \
+            if (ablation_flags(u.flags) & kFlagNoFullTest) u.head = u.tail;                  \
+            batch = issue_batch(sh, u, false);                                               \
+            inflight = batch.n != 0;                                                         \
         }                                                                                    \
     }
 
-    static_assert(K == 8 || K == 16, "ring of 8 or 16 rows (a power of two: row codes OR together)");
-    static_assert((K / kIssue) % kSweepBatchSlots == 0 || kSweepBatchSlots == 1,
-                  "issue points per loop body must cycle through the batch slots");
+    static_assert(K == 8, "the loop body below is 8 steps (a power of two: row codes OR together)");
     for (int i0 = 0; i0 < T; i0 += K) {
         // FIFO code of row ys + i0 + J: i0 is a multiple of K, so its spread ORs with J's
         const uint32_t lane_row_code = lane_code | spread_code((uint32_t)i0 << 6);
@@ -847,24 +766,10 @@ __device__ __forceinline__ void sweep_unit(const SweepShared& sh, UnitCtx& u, co
         FDF_SWEEP_STEP(5) FDF_STEP_EXIT(5)
         FDF_SWEEP_STEP(6) FDF_STEP_EXIT(6)
         FDF_SWEEP_STEP(7)
-        if constexpr (K >= 12) {
-            FDF_STEP_EXIT(7)
-            FDF_SWEEP_STEP(8) FDF_STEP_EXIT(8)
-            FDF_SWEEP_STEP(9) FDF_STEP_EXIT(9)
-            FDF_SWEEP_STEP(10) FDF_STEP_EXIT(10)
-            FDF_SWEEP_STEP(11)
-        }
-        if constexpr (K >= 16) {
-            FDF_STEP_EXIT(11)
-            FDF_SWEEP_STEP(12) FDF_STEP_EXIT(12)
-            FDF_SWEEP_STEP(13) FDF_STEP_EXIT(13)
-            FDF_SWEEP_STEP(14) FDF_STEP_EXIT(14)
-            FDF_SWEEP_STEP(15)
-        }
 #undef FDF_STEP_EXIT
     }
 #undef FDF_SWEEP_STEP
-    flush_tests<NMS, N, LC>(sh, u, lk, inflight, batch);
+    flush_tests<NMS, N>(sh, u, lk, inflight, batch);
 }
 
 // Three bitmap bits of one bitmap row: columns x-1, x, x+1 (x-1 >= 2, x+1 < W - 3).  Both
@@ -876,8 +781,8 @@ __device__ __forceinline__ uint32_t bits3(const uint32_t* row, int x) {
 
 // Raster rank of bitmap position (row, x): keypoints before it in the band's bitmap.
 // bprefix[row * nb + k] counts the keypoints before word 4k within the row and rprefix[row]
-// those of the rows above (FDF_RANK_2PASS 0: bprefix holds their sum); the position's
-// 4-word block is one 16-byte LDS read (bitmap rows are whole blocks, bitmap_words_per_row).
+// those of the rows above, a word most lanes of a wave share; the position's 4-word block is
+// one 16-byte LDS read (bitmap rows are whole blocks, bitmap_words_per_row).
 __device__ __forceinline__ uint32_t bitmap_rank(const uint32_t* bitmap, const uint16_t* bprefix,
                                                 const uint32_t* rprefix, uint32_t nw,
                                                 uint32_t nb, uint32_t row, uint32_t x) {
@@ -885,11 +790,7 @@ __device__ __forceinline__ uint32_t bitmap_rank(const uint32_t* bitmap, const ui
     const uint32_t wi = x >> 5, blk = wi / kRankBlock, j = wi % kRankBlock;
     const uint4 q = reinterpret_cast<const uint4*>(bitmap + row * nw)[blk];
     uint32_t r = bprefix[row * nb + blk];
-#if FDF_RANK_2PASS
     r += rprefix[row];
-#else
-    (void)rprefix;
-#endif
     r += j > 0 ? (uint32_t)__popc(q.x) : 0u;
     r += j > 1 ? (uint32_t)__popc(q.y) : 0u;
     r += j > 2 ? (uint32_t)__popc(q.z) : 0u;
@@ -908,9 +809,10 @@ __device__ __forceinline__ uint32_t neighbour_bits(const uint32_t* bitmap, uint3
 }
 
 // Rank prefixes of the band's keypoint bitmap (R2 rows): bprefix[row * nb + k] = keypoints
-// before word 4k of the row, rprefix[row] = keypoints of the rows above (FDF_RANK_2PASS 0:
-// added to the block prefixes in a third pass).  Returns the bitmap's keypoint total (every
-// thread).
+// before word 4k of the row, rprefix[row] = keypoints of the rows above.  The block prefixes
+// stay row-relative (bitmap_rank adds the row's prefix).  u16 holds them: a row-relative
+// prefix is never larger than the band's keypoint count, and the ranked tiers hold at most
+// nms_area_entries keypoints.  Returns the bitmap's keypoint total (every thread).
 __device__ uint32_t band_rank_prefixes(const uint32_t* bitmap, uint32_t R2, uint32_t nw,
                                        uint16_t* bprefix, uint32_t* rprefix, uint32_t* total) {
     const uint32_t tid = threadIdx.x, lane = tid & 63;
@@ -978,20 +880,6 @@ __device__ uint32_t band_rank_prefixes(const uint32_t* bitmap, uint32_t R2, uint
         if (lane == 0) *total = carry;
     }
     __syncthreads();
-#if !FDF_RANK_2PASS
-    // block prefixes absolute (the rows above included): one read per rank (u16 holds them:
-    // the ranked tiers hold at most nms_area_entries keypoints)
-    {
-        const RowDiv nbd = make_rowdiv(nb_blocks);
-        for (uint32_t i = tid; i < R2 * nb_blocks; i += kThreads)
-            bprefix[i] = (uint16_t)(bprefix[i] + rprefix[udiv(i, nbd)]);
-    }
-    __syncthreads();
-#endif
-    // (FDF_RANK_2PASS: the block prefixes stay row-relative and bitmap_rank adds the row's
-    // prefix, a word most lanes of a wave share.  u16 still holds them: a row-relative prefix is
-    // never larger than the absolute one, and the ranked tiers hold at most nms_area_entries
-    // keypoints)
     return *total;
 }
 
@@ -1269,14 +1157,6 @@ __device__ uint64_t band_lookback(const BandParams& P, uint32_t task, uint32_t t
     // tail.
 __device__ __forceinline__ uint32_t band_task(const BandParams& P) {
     const uint32_t b = blockIdx.x;
-#ifdef FDF_LINEAR_TASKS
-    {   // A/B variant: block b -> the b-th band in raster order over the whole grid (the
-        // frames' full bands first, their last bands at the end), no XCD ranges
-        const uint32_t B = P.bands_per_frame, nfull = (P.ntasks / B) * (B - 1);
-        if (B <= 1) return b;
-        return b < nfull ? (b / (B - 1)) * B + b % (B - 1) : (b - nfull) * B + (B - 1);
-    }
-#endif
     const uint32_t q8 = P.ntasks >> 3, r8 = P.ntasks & 7, k8 = b & 7;
     const uint32_t c0 = k8 * q8 + min(k8, r8), j = b >> 3;
     uint32_t task = c0 + j;
@@ -1301,7 +1181,6 @@ __device__ __forceinline__ uint32_t band_task(const BandParams& P) {
 template <int NMS, int N>
 __device__ __forceinline__ uint32_t sweep_band(const BandParams& P, uint8_t* smem_raw, uint32_t task,
                                               uint64_t (&ph)[4]) {
-    constexpr int LC = kLaneCols;
     const SweepLayout L = make_sweep_layout(P.rows, P.words_per_row, NMS);
     const uint32_t tid = threadIdx.x;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1324,10 +1203,8 @@ __device__ __forceinline__ uint32_t sweep_band(const BandParams& P, uint8_t* sme
     }
     uint32_t* unit_ctr = wave_sum + kWaves;
     static_assert(kThreads == 256, "one table entry per thread");
-#if FDF_SELTAB_CONST
     // select_bit's table entry of byte tid, loaded before the bitmap clear that hides it
     const uint32_t sel_word = kSelTab.v[tid];
-#endif
     // the bitmap and its pad word, cleared 16 bytes per store up to the (16-byte aligned)
     // end of its LDS area
     for (uint32_t i = tid; i < L.pq / 16; i += kThreads)
@@ -1336,20 +1213,7 @@ __device__ __forceinline__ uint32_t sweep_band(const BandParams& P, uint8_t* sme
         unit_ctr[0] = 0;
         unit_ctr[1] = 0;
     }
-#if FDF_SELTAB_CONST
     reinterpret_cast<uint32_t*>(smem_raw + L.seltab)[tid] = sel_word;
-#else
-    {   // select_bit's table: the positions of byte tid's set bits, the k-th in nibble k
-        uint32_t word = 0, k = 0;
-#pragma unroll
-        for (uint32_t i = 0; i < 8; ++i) {
-            const uint32_t bit = (tid >> i) & 1u;
-            word |= bit ? i << (4u * k) : 0u;
-            k += bit;
-        }
-        reinterpret_cast<uint32_t*>(smem_raw + L.seltab)[tid] = word;
-    }
-#endif
     if (P.chunk_flags && wave == 0) {
         // an overlapped upload (fdf_detect): wave 0 waits for the chunk holding the last row
         // the band reads -- its tested rows (with the NMS halo row) + 3 -- then acquires at
@@ -1384,7 +1248,7 @@ __device__ __forceinline__ uint32_t sweep_band(const BandParams& P, uint8_t* sme
     sh.slist_n = unit_ctr + 1;
     // list positions take 20 bits (PosCode)
     sh.pc = make_poscode(W);
-    sh.slist_cap = pos_fits(sh.pc, rows + 2 * halo, W) ? kScoreListCap : 0u;
+    sh.slist_cap = pos_fits(sh.pc, rows + 2 * halo) ? kScoreListCap : 0u;
     sh.spill = reinterpret_cast<uint32_t*>(P.slots + (uint64_t)task * P.slot_bytes);
     sh.spill_cap = sh.slist_cap ? P.slot_bytes / 4 : 0u;
     sh.seltab = reinterpret_cast<const uint32_t*>(smem_raw + L.seltab);
@@ -1419,9 +1283,9 @@ __device__ __forceinline__ uint32_t sweep_band(const BandParams& P, uint8_t* sme
             unit = __builtin_amdgcn_readfirstlane(unit);
             if (unit >= nunits) break;
             const uint32_t strip = unit % P.nstrips, sub = unit / P.nstrips;
-            u.S = (int)strip * strip_cols(LC);
+            u.S = (int)strip * kStripCols;
             {   // first row whose last lane's window can end past W * H
-                const int last_end = u.S - LC + LC * 64;
+                const int last_end = u.S - kLaneCols + kLaneCols * 64;
                 const int num = (int)(W * H) - last_end;
                 u.src.tail_row = num < 0 ? 0 : num / (int)W + 1;
             }
@@ -1496,13 +1360,13 @@ __device__ __forceinline__ uint32_t sweep_band(const BandParams& P, uint8_t* sme
     const uint32_t gq = (ngroups + kWaves - 1) / kWaves;
     const uint32_t gb = min(wave * gq, ngroups), ge = min(gb + gq, ngroups);
     uint32_t mine = 0;
-#if FDF_EMIT_REGS
     // a wave's quarter of up to 64 * kEmitKeep groups (1080p: 353) stays in registers with
     // its counts for the write pass; a larger one is read and counted again there.  Max-t
-    // instances only: it removes 1.9 M VALU per 1080p launch there, adds 0.4 M to a SAD launch
-    // and changes nothing without NMS.
+    // instances of the units with kEmitRegs only: it removes 1.9 M VALU per 1080p launch
+    // there, adds 0.4 M to a SAD launch and changes nothing without NMS.
     constexpr uint32_t kEmitKeep = 6;
-    const bool in_regs = NMS == kNmsMaxThreshold && ge - gb <= 64 * kEmitKeep;   // wave-uniform
+    const bool in_regs = kEmitRegs && NMS == kNmsMaxThreshold &&
+                         ge - gb <= 64 * kEmitKeep;   // wave-uniform
     uint4 kq[kEmitKeep];
     uint32_t kc[kEmitKeep];
     if (in_regs) {
@@ -1513,11 +1377,11 @@ __device__ __forceinline__ uint32_t sweep_band(const BandParams& P, uint8_t* sme
             kc[j] = __popc(kq[j].x) + __popc(kq[j].y) + __popc(kq[j].z) + __popc(kq[j].w);
             mine += kc[j];
         }
-    } else
-#endif
-    for (uint32_t g = gb + lane; g < ge; g += 64) {
-        const uint4 q = keep4[g];
-        mine += __popc(q.x) + __popc(q.y) + __popc(q.z) + __popc(q.w);
+    } else {
+        for (uint32_t g = gb + lane; g < ge; g += 64) {
+            const uint4 q = keep4[g];
+            mine += __popc(q.x) + __popc(q.y) + __popc(q.z) + __popc(q.w);
+        }
     }
     const uint32_t wave_total = __builtin_amdgcn_readlane(wave_incl_scan(mine), 63);
     if (lane == 0) wave_sum[wave] = wave_total;
@@ -1570,17 +1434,16 @@ __device__ __forceinline__ uint32_t sweep_band(const BandParams& P, uint8_t* sme
                 ++idx;
             }
         };
-#if FDF_EMIT_REGS
         if (in_regs) {
 #pragma unroll
             for (uint32_t j = 0; j < kEmitKeep; ++j)
                 if (gb + 64 * j < ge) emit_round(gb + 64 * j, kq[j], kc[j]);
-        } else
-#endif
-        for (uint32_t g0 = gb; g0 < ge; g0 += 64) {
-            const uint32_t g = g0 + lane;
-            const uint4 q = g < ge ? keep4[g] : make_uint4(0u, 0u, 0u, 0u);
-            emit_round(g0, q, __popc(q.x) + __popc(q.y) + __popc(q.z) + __popc(q.w));
+        } else {
+            for (uint32_t g0 = gb; g0 < ge; g0 += 64) {
+                const uint32_t g = g0 + lane;
+                const uint4 q = g < ge ? keep4[g] : make_uint4(0u, 0u, 0u, 0u);
+                emit_round(g0, q, __popc(q.x) + __popc(q.y) + __popc(q.z) + __popc(q.w));
+            }
         }
     }
     if (!listed) {
@@ -1590,10 +1453,10 @@ __device__ __forceinline__ uint32_t sweep_band(const BandParams& P, uint8_t* sme
     return total;
 }
 
-// Occupancy target: kWavesEU waves per SIMD (4: 128 VGPRs each, 2: 256).
+// Occupancy target: kSweepWavesPerEU = 4 waves per SIMD (128 VGPRs each).
 template <int NMS, int N>
 __global__ __launch_bounds__(kThreads)
-__attribute__((amdgpu_waves_per_eu(kWavesEU, kWavesEU)))
+__attribute__((amdgpu_waves_per_eu(kSweepWavesPerEU, kSweepWavesPerEU)))
 void fast_sweep_kernel(BandParams P) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
     uint64_t t0 = 0, r0 = 0;
@@ -1660,8 +1523,6 @@ template <int NMS>
 static SweepKernelFn pick_sweep_n(uint32_t n) {
 #if defined(FDF_ISA_ONE_N)   // ISA studies only (tools/isa_loops.py): one count per NMS mode
     return n == FDF_ISA_ONE_N ? fast_sweep_kernel<NMS, FDF_ISA_ONE_N> : nullptr;
-#elif defined(FDF_AB_COUNTS)   // A/B variant builds (tools/build_variant.sh): the bench's n = 9, 12
-    return n == 9 ? fast_sweep_kernel<NMS, 9> : (n == 12 ? fast_sweep_kernel<NMS, 12> : nullptr);
 #else
     switch (n) {
         case 9: return fast_sweep_kernel<NMS, 9>;

@@ -1,15 +1,13 @@
 // fdf_sweep_latency.hip -- the grey detector for grids whose units end inside an 8-step block
 // (a single frame's short bands, fdf_api.cpp enqueue): fdf_sweep_impl.h with
-// FDF_SWEEP_TU_EXIT, so a unit stops at its last row instead of sweeping padding rows.
+// FDF_SWEEP_TU_EXIT 1, so a unit stops at its last row instead of sweeping padding rows.
 #define FDF_SWEEP_RGB 0
 #define FDF_SWEEP_NS grey_lat
 #define FDF_SWEEP_TU_EXIT 1
-// The emit's register-resident write pass (FDF_EMIT_REGS) makes these instances' max-t kernels
-// spill (512-528 bytes of scratch per lane; single frame max-t 16.8 -> 26.1 us): off here
-// unless a variant build sets the switch itself.
-#ifndef FDF_EMIT_REGS
-#define FDF_EMIT_REGS 0
-#endif
+// The emit's register-resident write pass (FDF_SWEEP_TU_EMIT_REGS) makes these instances'
+// max-t kernels spill (512-528 bytes of scratch per lane; single frame max-t 16.8 -> 26.1 us):
+// off here.
+#define FDF_SWEEP_TU_EMIT_REGS 0
 #include "fdf_sweep_impl.h"
 
 namespace fdfk {

@@ -1,8 +1,8 @@
 #!/bin/bash
 # Build libfdf.so of the working tree with extra compile definitions into
 # build/libfdf_<NAME>.so, for A/B timing in one process pool:
-#   tools/build_variant.sh ring8 "-DFDF_RING_MAXT=8 -DFDF_RING_SAD=8"
-#   FDF_LIB_PATH=build/libfdf_ring8.so python tools/ablate.py ...
+#   tools/build_variant.sh debug "-DFDF_DEBUG_BUILD"
+#   FDF_LIB_PATH=build/libfdf_debug.so python tools/ablate.py ...
 set -e
 NAME=${1:?name}; DEFS=${2:-}
 ROOT=$(cd "$(dirname "$0")/.." && pwd)

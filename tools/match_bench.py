@@ -12,7 +12,7 @@ expanded to +-1 half precision, one matrix product per frame pair -- exact for 2
 and topk(2) per row, chunked to fit memory), alternating with the HIP path in one process;
 the distances must be equal at the timed size and the indices wherever the best distance is
 unique (topk's choice among equal values is not specified).  With --ab-lib a second build of
-the library (FDF_MATCH_SCALAR=1: scalar-load staging, no LDS) is timed in the same rounds.
+the library (any libfdf.so, e.g. one of another commit) is timed in the same rounds.
 Device events around back-to-back calls, every shape warmed first, profiler off.
 
     python tools/match_bench.py [--frames 512] [--calls 20] [--rounds 5] [--ab-lib SO] [--out FILE]
@@ -112,7 +112,7 @@ def main(argv=None):
     ap.add_argument("--calls", type=int, default=20, help="back-to-back HIP calls per timing")
     ap.add_argument("--torch-calls", type=int, default=1)
     ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--ab-lib", default="", help="a FDF_MATCH_SCALAR=1 build to time alongside")
+    ap.add_argument("--ab-lib", default="", help="a second libfdf.so build to time alongside")
     ap.add_argument("--out", default="")
     args = ap.parse_args(argv)
 
