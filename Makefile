@@ -8,6 +8,7 @@
 #                          fdf::match_descriptors, fdf::resize / fdf::build_pyramid,
 #                          fdf::estimate_model
 #   tests/cpp/test_wg_share  host-only check of the kernels' work split (fdf_common.h)
+#   tests/cpp/test_geometry  host-only table of the band geometry and launch plan (fdf_geometry.h)
 HIPCC ?= /opt/rocm/bin/hipcc
 CC ?= gcc
 CXX ?= g++
@@ -22,7 +23,8 @@ OBJS := $(addprefix $(CSRC)/fdf_,$(addsuffix .o,kernels sweep sweep_latency swee
 HEADERS := $(wildcard $(CSRC)/*.h) include/fdf.h
 CPP_TESTS := $(addprefix tests/cpp/test_cpp_,api select orient harris describe match pyramid ransac)
 
-all: $(LIBFDF) oracle/liboracle.so oracle/libfast_avx2.so $(CPP_TESTS) tests/cpp/test_wg_share
+all: $(LIBFDF) oracle/liboracle.so oracle/libfast_avx2.so $(CPP_TESTS) tests/cpp/test_wg_share \
+	tests/cpp/test_geometry
 
 $(CSRC)/%.o: $(CSRC)/%.hip $(HEADERS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -46,6 +48,9 @@ tests/cpp/%: tests/cpp/%.cpp include/fdf.hpp include/fdf.h $(LIBFDF)
 tests/cpp/test_wg_share: tests/cpp/test_wg_share.cpp $(CSRC)/fdf_common.h $(CSRC)/fdf_kernels.h
 	$(HIPCC) -x hip --offload-host-only -O2 -std=c++17 -Wall -o $@ $<
 
+tests/cpp/test_geometry: tests/cpp/test_geometry.cpp $(CSRC)/fdf_geometry.h $(CSRC)/fdf_kernels.h include/fdf.h
+	$(HIPCC) -x hip --offload-host-only -O2 -std=c++17 -Wall -o $@ $<
+
 # Ablation build (tools/ablate.py, tools/pmc_ablate.sh): the same library with the internal
 # FDF_DEBUG_FLAGS / FDF_NSUB / FDF_LDS_BUDGET / FDF_COMPACT_TPG switches compiled in.
 debug: build/libfdf_debug.so
@@ -54,6 +59,7 @@ build/libfdf_debug.so: $(CSRC)/*.hip $(CSRC)/*.cpp $(CSRC)/*.h include/fdf.h
 	bash tools/build_variant.sh debug "-DFDF_DEBUG_BUILD"
 
 clean:
-	rm -f $(CSRC)/*.o $(LIBFDF) oracle/*.so $(CPP_TESTS) tests/cpp/test_wg_share
+	rm -f $(CSRC)/*.o $(LIBFDF) oracle/*.so $(CPP_TESTS) tests/cpp/test_wg_share \
+		tests/cpp/test_geometry
 
 .PHONY: all clean debug

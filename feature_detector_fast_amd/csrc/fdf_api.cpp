@@ -21,6 +21,7 @@
 
 #include "../../include/fdf.h"
 #include "fdf_ctx.h"
+#include "fdf_geometry.h"
 
 constexpr size_t kMaxTimedCalls = 4096;
 constexpr uint64_t kDefaultMinTasks = 1024;   // 4 workgroups on each of 256 CUs
@@ -122,122 +123,6 @@ int ensure_host(fdf_ctx* ctx, T** buf, T** dev, size_t* have, size_t need, hipSt
     return FDF_OK;
 }
 
-// Band geometry of the sweep kernel.  A band is R full-width centre rows; its 4 waves take
-// units = column strips (992 centres) x sub-bands.  Tall bands amortise the 8-row halo of a
-// sub-band; short bands give a small job (one frame) enough workgroups.  The LDS footprint
-// is kept <= 40 KB so 4 workgroups fit a CU.
-struct Geometry {
-    uint32_t R, nstrips, nsub;
-};
-
-
-Geometry pick_geometry(uint32_t n_frames, uint32_t w, uint32_t h, uint32_t nms,
-                       uint64_t slots, double density, uint32_t forced_rows,
-                       bool host_src = false) {
-    Geometry g;
-    const uint32_t sc = (uint32_t)fdfk::kStripCols;
-    g.nstrips = (w - 3 + sc - 1) / sc;
-    // >= 4 units per band (one per wave), handed out dynamically; taller units (fewer halo
-    // rows) measured faster than more, shorter units for balance
-    g.nsub = (4 + g.nstrips - 1) / g.nstrips;
-#ifdef FDF_DEBUG_BUILD   // ablation builds only (libfdf_debug.so)
-    if (const char* e = std::getenv("FDF_NSUB")) g.nsub = std::max(1ul, std::strtoul(e, nullptr, 0));
-#endif
-    const uint32_t centre_rows = h - 6;
-    const uint32_t nw = fdfk::bitmap_words_per_row(w);
-    // extra rows a unit tests: NMS bands test one row above and below (first / last unit)
-    const uint32_t halo = fdfk::band_halo(nms) * (g.nsub == 1 ? 2u : 1u);
-    // LDS per workgroup sets the workgroups per CU: <= 40 KB keeps 4.
-    // Without NMS a 35 KB budget (bands of ~122 rows at 1080p) measured faster than the
-    // tallest band that fits (more, shorter workgroups: a shorter grid tail).
-    uint32_t budget = (nms ? 40000u : 35000u);
-#ifdef FDF_DEBUG_BUILD
-    if (const char* b = std::getenv("FDF_LDS_BUDGET"))
-        budget = std::min<uint32_t>(fdfk::kSweepMaxLds, (uint32_t)std::strtoul(b, nullptr, 0));
-#endif
-    // The band height with the shortest modelled launch (in sweep-step units): every unit
-    // costs its steps plus kUnitCost (prologue, flush, unit hand-out), every workgroup
-    // kBandCost more (LDS clear, NMS pass, emit), and the grid runs on `slots` workgroup
-    // slots at once -- time = max(total / slots, one workgroup) + half a workgroup of tail
-    // (workgroups of one height differ with their rows' content, up to ~1.5x).  So a grid
-    // that cannot fill the chip takes the shortest bands (lowest latency), a large batch
-    // the tallest that waste no padding steps, and a grid near one round of the chip neither
-    // spills into a second round nor leaves slots idle.  slots = 1 (fdf_ctx_set_geometry,
-    // tests) gives a small job the full-size geometry (tall bands, long units); the
-    // keypoints are the same either way.
-    // NMS: when an earlier launch of this configuration measured the keypoint density, keep
-    // a band's expected keypoints (x1.2) within the LDS score list, so that few bands
-    // spill (4K t=8 n=12 SAD: 38-row bands; margins 1.5 / 1.2 / 1.0 / 0.8 measured 0.726 /
-    // 0.716 / 0.715 / 0.730 ms, profiles/r03/l4_margin_4k.json)
-    uint32_t max_rows = 256;
-    double margin = 1.2;
-#ifdef FDF_DEBUG_BUILD
-    if (const char* e = std::getenv("FDF_DENSITY_MARGIN")) margin = std::strtod(e, nullptr);
-#endif
-    if (nms && density > 0.0 && margin > 0.0) {
-        const double rows = (double)fdfk::kScoreListCap / (margin * density * (double)w) - 2.0;
-        max_rows = rows < (double)g.nsub ? g.nsub : (rows > 256.0 ? 256u : (uint32_t)rows);
-    }
-    if (forced_rows) {   // fdf_ctx_set_band_rows: the height asked for, as far as LDS allows
-        g.R = (forced_rows + g.nsub - 1) / g.nsub * g.nsub;
-        while (g.R > g.nsub && fdfk::make_sweep_layout(g.R, nw, nms).total > fdfk::kSweepMaxLds)
-            g.R -= g.nsub;
-        return g;
-    }
-    constexpr double kUnitCost = 3.0;
-    const double band_cost = nms ? 4.0 : 2.0;
-    const uint32_t units_per_wave = (g.nstrips * g.nsub + fdfk::kWaves - 1) / fdfk::kWaves;
-    // A grid that fits one round of the chip (a single frame) is latency-bound, one wave per
-    // SIMD: a unit's padding steps past its last row (the sweep runs whole 8-step blocks) load
-    // nothing and cost a quarter of a real step, and every band's look-back polls the
-    // descriptors of the bands before it, one round per 64.  Measured on one device-resident
-    // 1080p frame (profiles/r05/e7_single_frame_rows/, sweep us at 4 / 6 / 8 / 10 / 14 / 20 rows):
-    // max-t 19.0 / 17.2 / 17.8 / 18.1 / 19.4 / 22.6, NMS off 15.0 / 13.3 / 13.4 / 13.5 / 13.9 /
-    // 17.1 -- this model picks 6 rows for both (14 and 16 before).  A frame read in place over
-    // PCIe keeps the full-step model: its halo rows cost PCIe bytes, and 6-10 rows measured
-    // within noise of 14 there (r5_e8_host_rows_*.json).
-    auto wg_cost = [&](uint32_t rows, bool latency) {
-        const uint32_t unit_rows = (rows + g.nsub - 1) / g.nsub;
-        const double steps = (double)fdfk::sweep_steps(unit_rows, halo);
-        const double real = std::min(steps, (double)(unit_rows + halo));
-        return units_per_wave * ((latency ? real + 0.25 * (steps - real) : steps) + kUnitCost) +
-               band_cost;
-    };
-    const uint64_t one_round = std::min<uint64_t>(slots, fdfk::kDirectMaxTasks);
-    auto pick = [&](bool latency) {
-        double best = 0.0;
-        uint32_t best_R = 0;
-        for (uint32_t R = g.nsub; R <= max_rows && R < centre_rows + g.nsub; R += g.nsub) {
-            if (fdfk::make_sweep_layout(R, nw, nms).total > budget) break;
-            const uint32_t bands = (centre_rows + R - 1) / R;
-            const uint64_t ntasks = (uint64_t)n_frames * bands;
-            if (latency && ntasks > one_round) continue;   // stays one round of the chip
-            const double lookback = latency ? (double)((ntasks + 63) / 64) : 0.0;
-            const double full = wg_cost(R, latency) + lookback;
-            const double last = wg_cost(centre_rows - (bands - 1) * R, latency) + lookback;
-            const double total = (double)n_frames * ((bands - 1) * full + last);
-            const double t = std::max(total / (double)slots, full) + 0.5 * full;
-            if (best_R == 0 || t <= best * 1.001) {  // ties: the taller band (fewer workgroups)
-                best = t;
-                best_R = R;
-            }
-        }
-        return best_R;
-    };
-    g.R = pick(false);
-    // the grid of that height fits one round of the chip: the latency model picks among the
-    // heights that keep it so
-    if (!host_src && g.R && (uint64_t)n_frames * ((centre_rows + g.R - 1) / g.R) <= one_round) {
-        const uint32_t r = pick(true);
-        if (r) g.R = r;
-    }
-    if (g.R == 0) g.R = g.nsub;
-    return g;
-}
-
-// Enqueue detection + compaction over `n_frames` device frames (w, h >= 7) on `stream`,
-// after the context's previous device work (which may have run on another stream: the
-// workspace is shared).
 // The direct output's look-back error word (h_stats[1]): set by a band whose wait ran out.
 volatile uint32_t* lookback_error_word(fdf_ctx* ctx) {
     return ctx->h_stats ? reinterpret_cast<volatile uint32_t*>(ctx->h_stats + 1) : nullptr;
@@ -297,71 +182,79 @@ struct ChunkedUpload {
     uint32_t rows = 0, epoch = 0;
 };
 
-int enqueue(fdf_ctx* ctx, const uint8_t* d_frames, uint32_t n_frames, uint32_t w, uint32_t h,
-            uint64_t frame_stride, const fdf_config* cfg, uint2* d_out, uint64_t cap,
-            uint64_t* d_offsets, hipStream_t stream, bool rgb = false,
-            const ChunkedUpload& up = ChunkedUpload{}, bool host_src = false) {
-    double density = 0.0;
-    if (!ctx->h_stats) {
-        void* hp = nullptr;
-        void* dp = nullptr;
-        if (hipHostMalloc(&hp, 64, hipHostMallocMapped) == hipSuccess &&
-            hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) {
-            ctx->h_stats = static_cast<uint64_t*>(hp);
-            ctx->d_stats = static_cast<uint64_t*>(dp);
-            std::memset(hp, 0, 64);
-        } else if (hp) {
-            (void)hipHostFree(hp);
-        }
-    }
-    if (cfg->nms) {
-        if (ctx->h_stats) {
-            const uint64_t v = *reinterpret_cast<volatile uint64_t*>(ctx->h_stats);
-            const uint32_t seq = (uint32_t)(v >> 32);
-            const fdf_ctx::LaunchInfo& li = ctx->hist[seq % 64];
-            if (seq != 0 && li.seq == seq && li.pixels > 0) {
-                ctx->known[li.nms % 3] = li;
-                ctx->known_density[li.nms % 3] = (double)(uint32_t)v / li.pixels;
-            }
-            const fdf_ctx::LaunchInfo& k = ctx->known[cfg->nms % 3];
-            if (k.seq != 0 && k.t == cfg->threshold && k.n == cfg->count && k.nms == cfg->nms &&
-                k.w == w)
-                density = ctx->known_density[cfg->nms % 3];
-        }
-    }
-    // workgroup slots of the device: 4 per CU (4 waves per SIMD); fdf_ctx_set_geometry's
-    // min_tasks replaces it (1: the tall bands of a large batch for any job)
-    const uint64_t per_cu = 4;
-    const uint64_t slots = ctx->min_tasks ? ctx->min_tasks
-                                          : (ctx->cus ? per_cu * ctx->cus : kDefaultMinTasks);
-    const Geometry geo = pick_geometry(n_frames, w, h, cfg->nms, slots, density, ctx->band_rows,
-                                       host_src);
-    const uint32_t R = geo.R;
-    const uint32_t nw = fdfk::bitmap_words_per_row(w);
+// The switches of the ablation build (libfdf_debug.so; see fdf_kernels.h), read at every call:
+// tools/ablate.py changes them between calls.  The release library reads no environment and
+// gets the defaults.
+struct DebugKnobs {
+    GeometryKnobs geo;            // FDF_NSUB, FDF_LDS_BUDGET, FDF_DENSITY_MARGIN, FDF_COMPACT_TPG, FDF_DIRECT
+    bool geometry_log = false;    // FDF_GEOMETRY_LOG: one line per launch on stderr
+    uint32_t flags = 0;           // FDF_DEBUG_FLAGS: BandParams::flags
+    bool stamps = false;          // FDF_STAMPS: per-workgroup stamps (fdf_debug_stamps)
+    bool set_chunks = false;      // FDF_CHUNKS: written to ctx->chunks (A/B of the overlapped
+    uint32_t chunks = 0;          // upload, tools/host_latency.py: 1 disables it)
+};
+
+DebugKnobs debug_knobs() {
+    DebugKnobs k;
 #ifdef FDF_DEBUG_BUILD
-    if (std::getenv("FDF_GEOMETRY_LOG"))
-        std::fprintf(stderr, "fdf geometry: %u x %ux%u nms=%u t=%u n=%u density=%.5f R=%u nsub=%u\n",
-                     n_frames, w, h, (unsigned)cfg->nms, (unsigned)cfg->threshold,
-                     (unsigned)cfg->count, density, R, geo.nsub);
+    unsigned long v = 0;
+    auto number = [&v](const char* name) {
+        const char* e = std::getenv(name);
+        if (e) v = std::strtoul(e, nullptr, 0);
+        return e != nullptr;
+    };
+    if (number("FDF_NSUB")) k.geo.nsub = (uint32_t)std::max(1ul, v);
+    if (number("FDF_LDS_BUDGET"))
+        k.geo.lds_budget_nms = k.geo.lds_budget_plain = std::min<uint32_t>(fdfk::kSweepMaxLds, (uint32_t)v);
+    if (const char* e = std::getenv("FDF_DENSITY_MARGIN")) k.geo.density_margin = std::strtod(e, nullptr);
+    if (number("FDF_COMPACT_TPG"))
+        k.geo.compact_tpg = std::max(1u, std::min((uint32_t)fdfk::kCompactTasks, (uint32_t)v));
+    if (number("FDF_DIRECT")) k.geo.allow_direct = v != 0;
+    k.geometry_log = std::getenv("FDF_GEOMETRY_LOG") != nullptr;
+    if (number("FDF_DEBUG_FLAGS")) k.flags = (uint32_t)v;
+    k.stamps = std::getenv("FDF_STAMPS") != nullptr;
+    if ((k.set_chunks = number("FDF_CHUNKS"))) k.chunks = (uint32_t)v;
 #endif
-    if (fdfk::make_sweep_layout(R, nw, cfg->nms).total > fdfk::kSweepMaxLds)
-        return FDF_ERR_SIZE;
-    const uint32_t bands = (h - 6 + R - 1) / R;
-    const uint64_t ntasks = (uint64_t)bands * n_frames;
-    if (ntasks == 0 || ntasks > 0x7fffffffull) return FDF_ERR_SIZE;
-    // A grid too small to fill the chip (a single frame) is latency-bound: its slots hold 4x
-    // the points (6% of the band's pixels instead of 1.6%), so that dense bands stay point
-    // lists and the compaction takes no bitmap expansion (a few hundred KB per frame)
-    // (fdf_ctx_set_geometry's forced full-size geometry keeps the full-size slots too)
-    const uint64_t fill = ctx->min_tasks ? ctx->min_tasks : kDefaultMinTasks;
-    const uint32_t slot_bytes = fdfk::slot_bytes_for(R, nw) * (ntasks < fill ? 4u : 1u);
-    uint32_t tpg = fdfk::compact_tasks_per_group((uint32_t)ntasks);
-    uint32_t flags = 0;
-#ifdef FDF_DEBUG_BUILD   // ablation builds only (libfdf_debug.so), see fdf_kernels.h
-    if (const char* e = std::getenv("FDF_COMPACT_TPG"))
-        tpg = std::max(1u, std::min((uint32_t)fdfk::kCompactTasks, (uint32_t)std::strtoul(e, nullptr, 0)));
-    if (const char* dbg = std::getenv("FDF_DEBUG_FLAGS")) flags = (uint32_t)std::strtoul(dbg, nullptr, 0);
-#endif
+    return k;
+}
+
+// ---- the steps of enqueue(), in its order ------------------------------------------------
+
+// First use: the context's two host-mapped words (h_stats[0] the NMS keypoint statistics,
+// h_stats[1] the look-back error word).  Without them the launches run with neither.
+void ensure_stats_word(fdf_ctx* ctx) {
+    if (ctx->h_stats) return;
+    void* hp = nullptr;
+    void* dp = nullptr;
+    if (hipHostMalloc(&hp, 64, hipHostMallocMapped) == hipSuccess &&
+        hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) {
+        ctx->h_stats = static_cast<uint64_t*>(hp);
+        ctx->d_stats = static_cast<uint64_t*>(dp);
+        std::memset(hp, 0, 64);
+    } else if (hp) {
+        (void)hipHostFree(hp);
+    }
+}
+
+// NMS: the keypoint density (per pixel, before suppression) the last finished launch of this
+// configuration measured, 0 when none did.  Takes the statistics word's news into `known`.
+double known_density(fdf_ctx* ctx, const fdf_config* cfg, uint32_t w) {
+    if (!cfg->nms || !ctx->h_stats) return 0.0;
+    const uint64_t v = *reinterpret_cast<volatile uint64_t*>(ctx->h_stats);
+    const uint32_t seq = (uint32_t)(v >> 32);
+    const fdf_ctx::LaunchInfo& li = ctx->hist[seq % 64];
+    if (seq != 0 && li.seq == seq && li.pixels > 0) {
+        ctx->known[li.nms % 3] = li;
+        ctx->known_density[li.nms % 3] = (double)(uint32_t)v / li.pixels;
+    }
+    const fdf_ctx::LaunchInfo& k = ctx->known[cfg->nms % 3];
+    if (k.seq != 0 && k.t == cfg->threshold && k.n == cfg->count && k.nms == cfg->nms && k.w == w)
+        return ctx->known_density[cfg->nms % 3];
+    return 0.0;
+}
+
+// `stream` follows the context's previous device work, whatever stream that ran on.
+int follow_last_enqueue(fdf_ctx* ctx, hipStream_t stream) {
     if (!ctx->done &&
         hipEventCreateWithFlags(&ctx->done, hipEventDisableTiming) != hipSuccess) {
         ctx->done = nullptr;
@@ -370,9 +263,15 @@ int enqueue(fdf_ctx* ctx, const uint8_t* d_frames, uint32_t n_frames, uint32_t w
     if (ctx->done_valid && ctx->done_stream != stream &&
         (record_done(ctx) != hipSuccess || hipStreamWaitEvent(stream, ctx->done, 0) != hipSuccess))
         return FDF_ERR_DEVICE;
+    return FDF_OK;
+}
+
+// The launch's workspace: band slots and counts, the group sums (zeroed again after a failed
+// launch), and for a direct launch the look-back descriptors and its tag (*epoch, else 0).
+int ensure_workspace(fdf_ctx* ctx, const LaunchPlan& pl, hipStream_t stream, uint32_t* epoch) {
     int rc;
-    if ((rc = ensure(ctx, &ctx->d_slots, &ctx->slots_bytes, (size_t)(ntasks * slot_bytes), stream))) return rc;
-    if ((rc = ensure(ctx, &ctx->d_counts, &ctx->counts_n, (size_t)ntasks, stream))) return rc;
+    if ((rc = ensure(ctx, &ctx->d_slots, &ctx->slots_bytes, (size_t)(pl.ntasks * pl.slot_bytes), stream))) return rc;
+    if ((rc = ensure(ctx, &ctx->d_counts, &ctx->counts_n, (size_t)pl.ntasks, stream))) return rc;
     if (!ctx->d_sums) {
         if (hipMalloc(reinterpret_cast<void**>(&ctx->d_sums),
                       (2 * fdfk::kMaxGroupSums + 4) * sizeof(uint32_t)) != hipSuccess) {
@@ -388,151 +287,185 @@ int enqueue(fdf_ctx* ctx, const uint8_t* d_frames, uint32_t n_frames, uint32_t w
         ctx->sums_dirty = false;
         ctx->ticket_next = 0;                       // the ticket counter is zero again
     }
-    // detection and compaction are two launches: a compaction fused into the detector's last
-    // workgroup measured 87 us for one frame against 13 + 12 us (every workgroup's device-scope
-    // release is an L2 writeback on gfx950)
-    // Small grids write their points directly (look-back, no compaction launch) when every
-    // workgroup is resident at once -- by the occupancy calculator for this instance and LDS
-    // size (4 per CU at 4 waves per SIMD) -- so that a band's look-back only waits for bands
-    // running beside it.  (Correctness does not depend on it: bands are numbered by their
-    // start tickets, band_lookback.)
-    const fdfk::SweepLayout lay = fdfk::make_sweep_layout(R, nw, cfg->nms);
-    const uint32_t wgs = wg_per_cu(ctx, cfg->nms, cfg->count, lay.total, rgb);
-    bool direct = ntasks <= std::min<uint64_t>(fdfk::kDirectMaxTasks, (uint64_t)ctx->cus * wgs);
-#ifdef FDF_DEBUG_BUILD
-    if (const char* e = std::getenv("FDF_DIRECT")) direct = direct && std::strtoul(e, nullptr, 0) != 0;
-#endif
-    const uint64_t ngroups = (ntasks + tpg - 1) / tpg;
-    const bool grouped = !direct && ngroups <= fdfk::kMaxGroupSums;
+    *epoch = 0;
+    if (!pl.direct) return FDF_OK;
+    // a (re)allocated buffer is zeroed: recycled device memory can hold descriptors of
+    // another context's launches.  Launch tags are unique in the process as well.
+    const size_t had = ctx->lookback_n;
+    if ((rc = ensure(ctx, &ctx->d_lookback, &ctx->lookback_n, (size_t)pl.ntasks, stream))) return rc;
+    if (ctx->lookback_n != had &&
+        hipMemsetAsync(ctx->d_lookback, 0, ctx->lookback_n * sizeof(uint64_t), stream) != hipSuccess)
+        return FDF_ERR_DEVICE;
+    *epoch = ++g_launch_epoch;
+    if (*epoch == 0) *epoch = ++g_launch_epoch;                    // 0 = a zeroed descriptor
+    return FDF_OK;
+}
+
+// The parameter blocks of a launch's two kernels.
+struct LaunchParams {
+    fdfk::BandParams p;
+    fdfk::CompactParams c;
+};
+
+// Both blocks over the workspace as it stands, what they share set once for both (no keypoint
+// statistics and no stamps yet).
+void fill_params(const fdf_ctx* ctx, const Geometry& geo, const LaunchPlan& pl,
+                 const uint8_t* d_frames, uint64_t frame_stride, uint32_t w, uint32_t h,
+                 const fdf_config* cfg, uint2* d_out, uint64_t cap, uint64_t* d_offsets,
+                 uint32_t epoch, const ChunkedUpload& up, uint32_t flags, LaunchParams* lp) {
+    fdfk::BandParams& p = lp->p;
+    fdfk::CompactParams& c = lp->c;
     uint32_t* sums_now = ctx->d_sums + (size_t)ctx->sums_parity * fdfk::kMaxGroupSums;
     uint32_t* sums_next = ctx->d_sums + (size_t)(1 - ctx->sums_parity) * fdfk::kMaxGroupSums;
-    fdfk::BandParams p;
+    p.width = c.width = w;
+    p.height = c.height = h;
+    p.rows = c.rows = geo.R;
+    p.bands_per_frame = c.bands_per_frame = pl.bands;
+    p.ntasks = c.ntasks = (uint32_t)pl.ntasks;
+    p.words_per_row = c.words_per_row = pl.nw;
+    p.slot_bytes = c.slot_bytes = pl.slot_bytes;
+    p.tasks_per_group = c.tasks_per_group = pl.tpg;
+    c.slots = p.slots = ctx->d_slots;
+    c.counts = p.counts = ctx->d_counts;
+    p.out = c.out = d_out;
+    p.cap = c.cap = cap;
+    p.frame_offsets = c.frame_offsets = d_offsets;
+    c.group_sums = p.group_sums = pl.grouped ? sums_now : nullptr;
+    p.kp_stats = c.kp_stats = nullptr;
+    // the detector's own
     p.frames = d_frames;
     p.frame_stride = frame_stride;
-    p.width = w;
-    p.height = h;
-    p.rows = R;
-    p.bands_per_frame = bands;
-    p.ntasks = (uint32_t)ntasks;
-    p.words_per_row = nw;
     p.threshold = cfg->threshold;
-    p.slot_bytes = slot_bytes;
-    p.slots = ctx->d_slots;
-    p.counts = ctx->d_counts;
     p.flags = flags;
     p.nstrips = geo.nstrips;
     p.nsub = geo.nsub;
-    fdfk::CompactParams c;
-    c.width = w;
-    c.height = h;
-    c.rows = R;
-    c.bands_per_frame = bands;
-    c.ntasks = (uint32_t)ntasks;
-    c.words_per_row = nw;
-    c.slot_bytes = slot_bytes;
-    c.tasks_per_group = tpg;
-    c.slots = ctx->d_slots;
-    c.counts = ctx->d_counts;
-    c.out = d_out;
-    c.cap = cap;
-    c.frame_offsets = d_offsets;
-    c.group_sums = grouped ? sums_now : nullptr;
-    c.next_sums = sums_next;
-    p.group_sums = grouped ? sums_now : nullptr;
-    p.tasks_per_group = tpg;
-    p.kp_stats = nullptr;
     p.stamps = nullptr;
-    p.direct = direct ? 1u : 0u;
-    p.epoch = 0;
-    p.lookback = nullptr;
-    p.out = d_out;
-    p.cap = cap;
-    p.frame_offsets = d_offsets;
+    p.direct = pl.direct ? 1u : 0u;
+    p.epoch = epoch;
+    p.lookback = pl.direct ? ctx->d_lookback : nullptr;
     p.ticket = ctx->d_sums + 2 * fdfk::kMaxGroupSums + 2;
     p.ticket_base = ctx->ticket_next;
     p.lookback_error = ctx->h_stats ? reinterpret_cast<uint32_t*>(ctx->d_stats + 1) : nullptr;
     p.chunk_flags = up.flags;
     p.chunk_rows = up.rows;
     p.chunk_epoch = up.epoch;
-    if (direct) {
-        // a (re)allocated buffer is zeroed: recycled device memory can hold descriptors of
-        // another context's launches.  Launch tags are unique in the process as well.
-        const size_t had = ctx->lookback_n;
-        if ((rc = ensure(ctx, &ctx->d_lookback, &ctx->lookback_n, (size_t)ntasks, stream))) return rc;
-        if (ctx->lookback_n != had &&
-            hipMemsetAsync(ctx->d_lookback, 0, ctx->lookback_n * sizeof(uint64_t), stream) != hipSuccess)
-            return FDF_ERR_DEVICE;
-        p.lookback = ctx->d_lookback;
-        uint32_t e = ++g_launch_epoch;
-        if (e == 0) e = ++g_launch_epoch;                          // 0 = a zeroed descriptor
-        p.epoch = e;
-    }
-#ifdef FDF_DEBUG_BUILD
-    if (std::getenv("FDF_STAMPS")) {
-        const size_t words = (size_t)ntasks * fdfk::kStampWords;
-        if ((rc = ensure(ctx, &ctx->d_stamps, &ctx->stamps_n, words, stream))) return rc;
-        p.stamps = ctx->d_stamps;
-        ctx->stamps_used = words;
-    }
-#endif
-    c.kp_stats = nullptr;
+    // the compaction's own
+    c.next_sums = sums_next;
     c.stats_out = nullptr;
     c.stats_seq = 0;
-    if (cfg->nms && ctx->h_stats && !direct) {
-        const uint32_t seq = ++ctx->stats_seq == 0 ? ++ctx->stats_seq : ctx->stats_seq;
-        fdf_ctx::LaunchInfo& li = ctx->hist[seq % 64];
-        li.seq = seq;
-        li.t = cfg->threshold;
-        li.n = cfg->count;
-        li.nms = cfg->nms;
-        li.w = w;
-        li.pixels = (double)n_frames * (double)w * (double)(h - 6);
-        p.kp_stats = ctx->d_sums + 2 * fdfk::kMaxGroupSums + 1;
-        c.kp_stats = p.kp_stats;
-        c.stats_out = ctx->d_stats;
-        c.stats_seq = seq;
+}
+
+// NMS with a compaction launch: the launch reports its keypoint total before suppression
+// under a new sequence number, and `hist` keeps what it was measured on (known_density).
+void open_density_record(fdf_ctx* ctx, const fdf_config* cfg, uint32_t n_frames, uint32_t w,
+                         uint32_t h, LaunchParams* lp) {
+    if (!cfg->nms || !ctx->h_stats || lp->p.direct) return;
+    const uint32_t seq = ++ctx->stats_seq == 0 ? ++ctx->stats_seq : ctx->stats_seq;
+    fdf_ctx::LaunchInfo& li = ctx->hist[seq % 64];
+    li.seq = seq;
+    li.t = cfg->threshold;
+    li.n = cfg->count;
+    li.nms = cfg->nms;
+    li.w = w;
+    li.pixels = (double)n_frames * (double)w * (double)(h - 6);
+    lp->p.kp_stats = lp->c.kp_stats = ctx->d_sums + 2 * fdfk::kMaxGroupSums + 1;
+    lp->c.stats_out = ctx->d_stats;
+    lp->c.stats_seq = seq;
+}
+
+// per-kernel timing: 4 events per call, timestamped by the dispatches themselves
+// (hipExtLaunchKernelGGL), so no marker packets sit between the kernels.  *ev: this call's
+// four, or NULL when it is not a timed one.
+int timing_events(fdf_ctx* ctx, hipEvent_t** ev) {
+    *ev = nullptr;
+    if (!ctx->timing || ctx->timing_calls++ % ctx->timing != 0 || ctx->timed >= kMaxTimedCalls)
+        return FDF_OK;
+    while (ctx->ev.size() < 4 * (ctx->timed + 1)) {
+        hipEvent_t e;
+        if (hipEventCreate(&e) != hipSuccess) return FDF_ERR_DEVICE;
+        ctx->ev.push_back(e);
     }
-    // per-kernel timing: 4 events per call, timestamped by the dispatches themselves
-    // (hipExtLaunchKernelGGL), so no marker packets sit between the kernels
-    hipEvent_t* ev = nullptr;
-    if (ctx->timing && ctx->timing_calls++ % ctx->timing == 0 && ctx->timed < kMaxTimedCalls) {
-        while (ctx->ev.size() < 4 * (ctx->timed + 1)) {
-            hipEvent_t e;
-            if (hipEventCreate(&e) != hipSuccess) return FDF_ERR_DEVICE;
-            ctx->ev.push_back(e);
-        }
-        ev = &ctx->ev[4 * ctx->timed];
-    }
-    // a small grid whose units are shorter than one 8-step block (a single frame's latency
-    // bands) runs the instances that leave the block at the unit's last row
-    // (fdf_sweep_latency.hip; 1080p NMS off 13.5 -> 12.5 us, max-t 17.3 -> 17.0 us per frame).
-    // Long units keep whole blocks: the exit tests cost the batch loop more than the padding
-    // steps they save (512 x 1080p NMS off, 61-row units: +0.6 %, profiles/r05/e16_*)
-    const uint32_t unit_steps = (R + geo.nsub - 1) / geo.nsub +
-                                fdfk::band_halo(cfg->nms) * (geo.nsub == 1 ? 2u : 1u);
-    const bool exit_in_block = !rgb && direct && unit_steps < fdfk::kSweepRing;
+    *ev = &ctx->ev[4 * ctx->timed];
+    return FDF_OK;
+}
+
+// The detector, and the compaction unless the bands write their points themselves.  A failed
+// launch may leave the group sums and the ticket counter half used: they are zeroed again.
+int launch_kernels(fdf_ctx* ctx, const LaunchParams& lp, const LaunchPlan& pl,
+                   const fdf_config* cfg, bool rgb, hipStream_t stream, hipEvent_t* ev) {
     auto launch = rgb ? fdfk::launch_sweep_rgb
-                      : (exit_in_block ? fdfk::launch_sweep_latency : fdfk::launch_sweep);
-    if (launch(p, cfg->nms, cfg->count, stream, ev ? ev[0] : nullptr, ev ? ev[1] : nullptr) !=
-        hipSuccess) {
+                      : (pl.exit_in_block ? fdfk::launch_sweep_latency : fdfk::launch_sweep);
+    if (launch(lp.p, cfg->nms, cfg->count, stream, ev ? ev[0] : nullptr, ev ? ev[1] : nullptr) !=
+            hipSuccess ||
+        (!pl.direct && fdfk::launch_compact(lp.c, stream, ev ? ev[2] : nullptr,
+                                            ev ? ev[3] : nullptr) != hipSuccess)) {
         ctx->sums_dirty = true;
         return FDF_ERR_DEVICE;
     }
-    if (direct) ctx->ticket_next += (uint32_t)ntasks;   // the launch takes one per workgroup
-    if (!direct && fdfk::launch_compact(c, stream, ev ? ev[2] : nullptr, ev ? ev[3] : nullptr) !=
-                       hipSuccess) {
-        ctx->sums_dirty = true;
-        return FDF_ERR_DEVICE;
-    }
-    if (grouped) ctx->sums_parity ^= 1;
-    if (ev) {
+    return FDF_OK;
+}
+
+// After the launches: tickets, the group sums' parity, the timed call, the compaction kept
+// for a relaunch (run_host) and the completion event.
+int note_launch(fdf_ctx* ctx, const LaunchParams& lp, const LaunchPlan& pl, bool timed,
+                hipStream_t stream) {
+    if (pl.direct) ctx->ticket_next += (uint32_t)pl.ntasks;   // the launch takes one per workgroup
+    if (pl.grouped) ctx->sums_parity ^= 1;
+    if (timed) {
         if (ctx->timed_compact.size() <= ctx->timed) ctx->timed_compact.resize(ctx->timed + 1);
-        ctx->timed_compact[ctx->timed] = direct ? 0 : 1;
+        ctx->timed_compact[ctx->timed] = pl.direct ? 0 : 1;
         ++ctx->timed;
     }
-    ctx->last_compact = c;
-    if (note_done(ctx, stream) != hipSuccess) return FDF_ERR_DEVICE;
-    return FDF_OK;
+    ctx->last_compact = lp.c;
+    return note_done(ctx, stream) == hipSuccess ? FDF_OK : FDF_ERR_DEVICE;
+}
+
+// Enqueue detection + compaction over `n_frames` device frames (w, h >= 7) on `stream`,
+// after the context's previous device work (which may have run on another stream: the
+// workspace is shared).
+int enqueue(fdf_ctx* ctx, const uint8_t* d_frames, uint32_t n_frames, uint32_t w, uint32_t h,
+            uint64_t frame_stride, const fdf_config* cfg, uint2* d_out, uint64_t cap,
+            uint64_t* d_offsets, hipStream_t stream, bool rgb = false,
+            const ChunkedUpload& up = ChunkedUpload{}, bool host_src = false) {
+    const DebugKnobs knobs = debug_knobs();
+    ensure_stats_word(ctx);
+    const double density = known_density(ctx, cfg, w);
+    // workgroup slots of the device: 4 per CU (4 waves per SIMD); fdf_ctx_set_geometry's
+    // min_tasks replaces it (1: the tall bands of a large batch for any job)
+    const uint64_t per_cu = 4;
+    const uint64_t slots = ctx->min_tasks ? ctx->min_tasks
+                                          : (ctx->cus ? per_cu * ctx->cus : kDefaultMinTasks);
+    const uint64_t fill = ctx->min_tasks ? ctx->min_tasks : kDefaultMinTasks;
+    const Geometry geo = pick_geometry(n_frames, w, h, cfg->nms, slots, density, ctx->band_rows,
+                                       host_src, knobs.geo);
+    if (knobs.geometry_log)
+        std::fprintf(stderr, "fdf geometry: %u x %ux%u nms=%u t=%u n=%u density=%.5f R=%u nsub=%u\n",
+                     n_frames, w, h, (unsigned)cfg->nms, (unsigned)cfg->threshold,
+                     (unsigned)cfg->count, density, geo.R, geo.nsub);
+    // (a band too large for the LDS has no occupancy to ask for: the plan reports it)
+    const uint32_t lds = sweep_lds(geo, w, cfg->nms);
+    const uint32_t wgs = lds <= fdfk::kSweepMaxLds ? wg_per_cu(ctx, cfg->nms, cfg->count, lds, rgb) : 0u;
+    const LaunchPlan pl = make_launch_plan(geo, n_frames, w, h, cfg->nms, rgb, fill, wgs, ctx->cus,
+                                           knobs.geo);
+    if (pl.status) return pl.status;
+    int rc;
+    uint32_t epoch;
+    if ((rc = follow_last_enqueue(ctx, stream))) return rc;
+    if ((rc = ensure_workspace(ctx, pl, stream, &epoch))) return rc;
+    LaunchParams lp;
+    fill_params(ctx, geo, pl, d_frames, frame_stride, w, h, cfg, d_out, cap, d_offsets, epoch, up,
+                knobs.flags, &lp);
+    if (knobs.stamps) {
+        const size_t words = (size_t)pl.ntasks * fdfk::kStampWords;
+        if ((rc = ensure(ctx, &ctx->d_stamps, &ctx->stamps_n, words, stream))) return rc;
+        lp.p.stamps = ctx->d_stamps;
+        ctx->stamps_used = words;
+    }
+    open_density_record(ctx, cfg, n_frames, w, h, &lp);
+    hipEvent_t* ev;
+    if ((rc = timing_events(ctx, &ev))) return rc;
+    if ((rc = launch_kernels(ctx, lp, pl, cfg, rgb, stream, ev))) return rc;
+    return note_launch(ctx, lp, pl, ev != nullptr, stream);
 }
 
 // The score reported with a keypoint: the NMS mode's own, max-threshold when NMS is off.
@@ -558,72 +491,192 @@ int check_host_args(const uint8_t* data, uint32_t n_frames, uint32_t w, uint32_t
     return FDF_OK;
 }
 
+// ---- the steps of run_host() ---------------------------------------------------------------
+
+// The host frames of a call: `n` frames of `h` rows of px * w bytes, the rows `row_stride`
+// and the frames `frame_stride` bytes apart.
+struct HostFrames {
+    const uint8_t* data;
+    uint32_t n, w, h;
+    size_t row_stride, frame_stride;
+    size_t px;                                     // bytes per pixel: 3 (RGB8) or 1
+    size_t row_bytes() const { return px * w; }
+    size_t frame_bytes() const { return px * w * h; }
+    size_t span() const {                          // first byte to last
+        return (size_t)(n - 1) * frame_stride + (size_t)(h - 1) * row_stride + px * w;
+    }
+};
+
+// The output of a host detection as the kernels address it.  `host`: the pinned,
+// device-mapped h_out / h_offs (the kernels write the points and offsets into host memory: no
+// copy back, one synchronisation); otherwise the device buffers d_out / d_offsets (the scored
+// calls, whose score kernel reads the points).
+struct HostOutput {
+    fdf_ctx* ctx;
+    bool host;
+    uint2* points() const { return host ? ctx->hd_out : ctx->d_out; }
+    uint64_t* offsets() const { return host ? ctx->hd_offs : ctx->d_offsets; }
+    size_t cap() const { return host ? ctx->h_out_points : ctx->out_points; }
+    int grow(size_t total) const {
+        return host ? ensure_host(ctx, &ctx->h_out, &ctx->hd_out, &ctx->h_out_points, total, ctx->stream)
+                    : ensure(ctx, &ctx->d_out, &ctx->out_points, total, ctx->stream);
+    }
+    int grow_offsets(size_t n) const {
+        return host ? ensure_host(ctx, &ctx->h_offs, &ctx->hd_offs, &ctx->h_offs_n, n, ctx->stream)
+                    : ensure(ctx, &ctx->d_offsets, &ctx->offsets_n, n, ctx->stream);
+    }
+};
+
+// Where a host range lies for the copy engines and the kernels: in pageable memory, inside
+// one pinned mapping (`dev`: the device address of its first byte, `flags`: the mapping's
+// allocation flags), or starting in a pinned mapping and running past it (a
+// hipHostRegister'ed range shorter than the frames).
+struct PinnedRange {
+    enum Kind { kPageable, kWhole, kPartial } kind;
+    const uint8_t* dev;
+    unsigned flags;
+};
+
+// The range's first and last bytes must both be pinned and map to one contiguous device range.
+PinnedRange probe_pinned(const uint8_t* p, size_t bytes) {
+    hipPointerAttribute_t a, z;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError();   // pageable memory: not an error here
+        return {PinnedRange::kPageable, nullptr, 0};
+    }
+    if (a.type != hipMemoryTypeHost || !a.devicePointer) return {PinnedRange::kPageable, nullptr, 0};
+    const uint8_t* dev = static_cast<const uint8_t*>(a.devicePointer);
+    bool whole = false;
+    if (hipPointerGetAttributes(&z, p + bytes - 1) == hipSuccess)
+        whole = z.type == hipMemoryTypeHost &&
+                static_cast<const uint8_t*>(z.devicePointer) == dev + (bytes - 1);
+    else
+        (void)hipGetLastError();   // the range runs past the pinned mapping
+    return {whole ? PinnedRange::kWhole : PinnedRange::kPartial, dev, a.allocationFlags};
+}
+
+// Frames that start in pinned host memory must lie inside one pinned mapping for the DMA
+// copies (the chunked upload's too): a range that runs past it is packed into the pinned
+// staging buffer by the CPU first, and `in` then describes the packed copy.
+int pack_to_staging(fdf_ctx* ctx, HostFrames* in) {
+    const size_t fb = in->frame_bytes(), rb = in->row_bytes();
+    const int rc = ensure_host(ctx, &ctx->h_stage, &ctx->hd_stage, &ctx->h_stage_bytes, fb * in->n,
+                               ctx->stream);
+    if (rc) return rc;
+    for (uint32_t f = 0; f < in->n; ++f)
+        for (uint32_t y = 0; y < in->h; ++y)
+            std::memcpy(ctx->h_stage + f * fb + (size_t)y * rb,
+                        in->data + f * in->frame_stride + (size_t)y * in->row_stride, rb);
+    in->data = ctx->h_stage;
+    in->row_stride = rb;
+    in->frame_stride = fb;
+    return FDF_OK;
+}
+
+// One grey frame to d_in in `nchunks` row chunks on the copy stream while the detector runs,
+// each band waiting for the chunk of its last row (`up`: what the detector needs for that).
+// A failure means the runtime cannot do this upload; the copy stream is drained.
+int upload_chunked(fdf_ctx* ctx, const HostFrames& in, uint32_t nchunks, ChunkedUpload* up) {
+    up->rows = (in.h + nchunks - 1) / nchunks;
+    up->epoch = ++ctx->chunk_epoch == 0 ? ++ctx->chunk_epoch : ctx->chunk_epoch;
+    up->flags = ctx->d_flags;
+    for (uint32_t r0 = 0, c = 0; r0 < in.h; r0 += up->rows, ++c) {
+        const uint32_t nr = std::min(up->rows, in.h - r0);
+        hipError_t e = upload_rows(ctx->d_in + (size_t)r0 * in.w, in.data + (size_t)r0 * in.row_stride,
+                                   in.row_stride, in.w, nr, ctx->copy_stream);
+        // the chunk's flag: a 4-byte copy behind it on the same (copy-engine) queue --
+        // hipStreamWriteValue32 is a kernel launch per call on this runtime (~20 us each)
+        ctx->h_flags[c] = up->epoch;
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(ctx->d_flags + c, ctx->h_flags + c, sizeof(uint32_t),
+                               hipMemcpyHostToDevice, ctx->copy_stream);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(ctx->copy_stream);
+            (void)hipGetLastError();
+            return FDF_ERR_DEVICE;
+        }
+    }
+    return FDF_OK;
+}
+
+// Every frame to `stage`, packed, on the context's stream before the launch.
+int upload_frames(fdf_ctx* ctx, const HostFrames& in, uint8_t* stage) {
+    for (uint32_t f = 0; f < in.n; ++f)
+        if (upload_rows(stage + (size_t)f * in.frame_bytes(), in.data + (size_t)f * in.frame_stride,
+                        in.row_stride, in.row_bytes(), in.h, ctx->stream) != hipSuccess)
+            return FDF_ERR_DEVICE;
+    return FDF_OK;
+}
+
+int run_host(fdf_ctx* ctx, const uint8_t* data, uint32_t n_frames, uint32_t w, uint32_t h,
+             size_t row_stride, size_t frame_stride, const fdf_config* cfg, bool rgb,
+             uint64_t* offs, bool host_out);
+
+// The overlapped upload failed or a band's wait for its chunk ran out: the call again with
+// one copy before the launch (counted; the caller's chunk setting stays).
+int retry_unchunked(fdf_ctx* ctx, const HostFrames& in, const fdf_config* cfg, uint64_t* offs,
+                    bool host_out) {
+    ++ctx->upload_fallbacks;
+    const uint32_t saved = ctx->chunks;
+    ctx->chunks = 1;
+    const int rc = run_host(ctx, in.data, in.n, in.w, in.h, in.row_stride, in.frame_stride, cfg,
+                            in.px == 3, offs, host_out);
+    ctx->chunks = saved;
+    return rc;
+}
+
+// The offsets on the host, once the stream's work is done: read in place (host output) or
+// copied back.
+hipError_t fetch_offsets(fdf_ctx* ctx, uint64_t* offs, uint32_t n_frames, bool host_out) {
+    hipError_t e = hipSuccess;
+    if (!host_out)
+        e = hipMemcpyAsync(offs, ctx->d_offsets, sizeof(uint64_t) * (n_frames + 1ull),
+                           hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = sync_own_stream(ctx);
+    if (e == hipSuccess && host_out)
+        std::memcpy(offs, ctx->h_offs, sizeof(uint64_t) * (n_frames + 1ull));
+    return e;
+}
+
 // Phase 1 of a host detection (lock held): frames in, detection + compaction into the
 // context's output buffer, frame offsets back to the host (`offs`, n_frames + 1 entries).
 // The output starts small and grows to the keypoint total; when it has to grow only the
 // compaction is run again (the per-band slots still hold the detection).  On success
 // ctx->last describes the result, which stays in the context until the next host call.
-// `host_out`: the output is the pinned, device-mapped h_out / h_offs (the kernels write the
-// points and offsets into host memory: no copy back, one synchronisation); otherwise the
-// device buffers d_out / d_offsets (the scored calls, whose score kernel reads the points).
+// `host_out`: see HostOutput.
 // `rgb`: the frames are RGB8 (rows of 3 * w bytes at row_stride), converted on the device
 // with image 0.24.6's to_luma8 before detection (src/main.rs:58).
 int run_host(fdf_ctx* ctx, const uint8_t* data, uint32_t n_frames, uint32_t w, uint32_t h,
              size_t row_stride, size_t frame_stride, const fdf_config* cfg, bool rgb,
              uint64_t* offs, bool host_out) {
     ctx->last = LastResult{};          // invalid, and not a shard of a multi-context call
+    HostFrames in{data, n_frames, w, h, row_stride, frame_stride, rgb ? 3u : 1u};
+    const HostOutput out{ctx, host_out};
     const size_t frame_bytes = (size_t)w * h;
     const size_t max_points = (size_t)(w - 6) * (h - 6) * n_frames;
     // first guess: 1 keypoint per 64 pixels (real images: 0.5-1.5 per 100)
     const size_t guess = std::min(max_points, std::max<size_t>(4096, frame_bytes / 64 * n_frames));
     int rc;
     if ((rc = ensure(ctx, &ctx->d_in, &ctx->in_bytes, frame_bytes * n_frames, ctx->stream))) return rc;
-    uint2* out_dev;                    // the output as the kernels address it
-    uint64_t* offs_dev;
-    size_t* out_cap;
-    if (host_out) {
-        if ((rc = ensure_host(ctx, &ctx->h_out, &ctx->hd_out, &ctx->h_out_points, guess, ctx->stream)))
-            return rc;
-        if ((rc = ensure_host(ctx, &ctx->h_offs, &ctx->hd_offs, &ctx->h_offs_n, n_frames + 1ull,
-                              ctx->stream)))
-            return rc;
-        out_dev = ctx->hd_out;
-        offs_dev = ctx->hd_offs;
-        out_cap = &ctx->h_out_points;
-    } else {
-        if ((rc = ensure(ctx, &ctx->d_out, &ctx->out_points, guess, ctx->stream))) return rc;
-        if ((rc = ensure(ctx, &ctx->d_offsets, &ctx->offsets_n, n_frames + 1ull, ctx->stream)))
-            return rc;
-        out_dev = ctx->d_out;
-        offs_dev = ctx->d_offsets;
-        out_cap = &ctx->out_points;
-    }
-    const size_t px = rgb ? 3 : 1;                 // bytes per pixel of the host frames
-    uint8_t* stage = ctx->d_in;
-    if (rgb) {
-        if ((rc = ensure(ctx, &ctx->d_rgb, &ctx->rgb_bytes, 3 * frame_bytes * n_frames, ctx->stream)))
-            return rc;
-        stage = ctx->d_rgb;
-    }
+    if ((rc = out.grow(guess))) return rc;
+    if ((rc = out.grow_offsets(n_frames + 1ull))) return rc;
+    if (rgb && (rc = ensure(ctx, &ctx->d_rgb, &ctx->rgb_bytes, 3 * frame_bytes * n_frames, ctx->stream)))
+        return rc;
     // the host frames are read by the copies below: nothing else may still read d_in (nor
     // the host output, which the host reads after this call)
     wait_done(ctx);
     // an error an earlier asynchronous fdf_detect_device left in the error word belongs to
     // that call: keep it for the next device call, so this call's own check sees only its own
     if (take_lookback_error(ctx)) ctx->pending_device_error = true;
+    const DebugKnobs knobs = debug_knobs();
+    if (knobs.set_chunks) ctx->chunks = knobs.chunks;
     // one grey frame of >= kChunkMinBytes: upload it in row chunks on the copy stream while
-    // the detector runs, each band waiting for the chunk of its last row (the H2D of a 1080p
-    // frame is ~45 us, the detector ~20 us: DESIGN.md §7.5)
-    ChunkedUpload up;
-#ifdef FDF_DEBUG_BUILD   // A/B of the overlapped upload (tools/host_latency.py): FDF_CHUNKS=1 disables it
-    if (const char* e = std::getenv("FDF_CHUNKS")) ctx->chunks = (uint32_t)std::strtoul(e, nullptr, 0);
-#endif
-    // (the chunk count in effect must be > 1: one chunk is one copy before the launch, which
-    // the plain path below does without the flag copy and the second stream)
-    const uint32_t nchunks_eff = std::min<uint32_t>(ctx->chunks ? ctx->chunks : kChunksDefault,
-                                                    kMaxChunks);
+    // the detector runs (the H2D of a 1080p frame is ~45 us, the detector ~20 us: DESIGN.md
+    // §7.5).  The chunk count in effect must be > 1: one chunk is one copy before the launch,
+    // which the plain upload does without the flag copy and the second stream
+    const uint32_t nchunks = std::min<uint32_t>(ctx->chunks ? ctx->chunks : kChunksDefault, kMaxChunks);
     const bool chunked = host_out && !rgb && n_frames == 1 && frame_bytes >= kChunkMinBytes &&
-                         nchunks_eff > 1 && ctx->h_stats && ensure_chunk_flags(ctx) == FDF_OK;
+                         nchunks > 1 && ctx->h_stats && ensure_chunk_flags(ctx) == FDF_OK;
     // one packed grey frame in pinned (page-locked, non-coherent) host memory, unscored: the
     // detector reads it in place over PCIe, with no copy before the launch -- its row stream
     // is the upload (1080p max-t 72-75 vs 82-83 us end to end).  Host writes
@@ -631,108 +684,17 @@ int run_host(fdf_ctx* ctx, const uint8_t* data, uint32_t n_frames, uint32_t w, u
     // acquire; a wave-level acquire fence cost ~20 us and changed no result:
     // tests/test_gpu_host_inplace.py reuses one buffer for different frames).  The frame is
     // then not in d_in: a result that does not fit the caller's buffer copies it there for
-    // fdf_fetch_last (detect_host).
-    const uint8_t* in_place = nullptr;
-    if (ctx->chunks == 0 && host_out && !rgb && n_frames == 1 && row_stride == w) {
-        // the frame's first and last bytes must both be pinned and map to one contiguous
-        // device range: a hipHostRegister'ed sub-range shorter than the frame is copied, not
-        // read past its end
-        hipPointerAttribute_t a, z;
-        if (hipPointerGetAttributes(&a, data) == hipSuccess) {
-            if (a.type == hipMemoryTypeHost && a.devicePointer &&
-                !(a.allocationFlags & hipHostMallocCoherent)) {
-                const uint8_t* last = data + frame_bytes - 1;
-                if (hipPointerGetAttributes(&z, last) == hipSuccess) {
-                    if (z.type == hipMemoryTypeHost && z.devicePointer &&
-                        static_cast<const uint8_t*>(z.devicePointer) ==
-                            static_cast<const uint8_t*>(a.devicePointer) + (frame_bytes - 1))
-                        in_place = static_cast<const uint8_t*>(a.devicePointer);
-                } else {
-                    (void)hipGetLastError();   // the frame runs past the pinned range
-                }
-            }
-        } else {
-            (void)hipGetLastError();   // pageable memory: not an error here
-        }
-    }
-    // frames that start in pinned host memory must lie inside one pinned mapping for the DMA
-    // copies below (the chunked upload's too); a range that runs past it is packed into the
-    // pinned staging buffer first
-    if (!in_place) {
-        const size_t span = (size_t)(n_frames - 1) * frame_stride + (size_t)(h - 1) * row_stride +
-                            px * w;
-        hipPointerAttribute_t a, z;
-        if (hipPointerGetAttributes(&a, data) == hipSuccess) {
-            if (a.type == hipMemoryTypeHost && a.devicePointer) {
-                const bool inside =
-                    hipPointerGetAttributes(&z, data + span - 1) == hipSuccess &&
-                    z.type == hipMemoryTypeHost &&
-                    static_cast<const uint8_t*>(z.devicePointer) ==
-                        static_cast<const uint8_t*>(a.devicePointer) + (span - 1);
-                if (!inside) {
-                    (void)hipGetLastError();
-                    const size_t fb = px * frame_bytes;
-                    if ((rc = ensure_host(ctx, &ctx->h_stage, &ctx->hd_stage, &ctx->h_stage_bytes,
-                                          fb * n_frames, ctx->stream)))
-                        return rc;
-                    for (uint32_t f = 0; f < n_frames; ++f)
-                        for (uint32_t y = 0; y < h; ++y)
-                            std::memcpy(ctx->h_stage + f * fb + (size_t)y * px * w,
-                                        data + f * frame_stride + (size_t)y * row_stride, px * w);
-                    data = ctx->h_stage;
-                    row_stride = px * w;
-                    frame_stride = fb;
-                }
-            }
-        } else {
-            (void)hipGetLastError();   // pageable memory
-        }
-    }
-    if (in_place) {
-    } else if (chunked) {
-        up.rows = (h + nchunks_eff - 1) / nchunks_eff;
-        up.epoch = ++ctx->chunk_epoch == 0 ? ++ctx->chunk_epoch : ctx->chunk_epoch;
-        up.flags = ctx->d_flags;
-        for (uint32_t r0 = 0, c = 0; r0 < h; r0 += up.rows, ++c) {
-            const uint32_t nr = std::min(up.rows, h - r0);
-            const uint8_t* src = data + (size_t)r0 * row_stride;
-            uint8_t* dst = ctx->d_in + (size_t)r0 * w;
-            hipError_t e = row_stride == w
-                               ? hipMemcpyAsync(dst, src, (size_t)nr * w, hipMemcpyHostToDevice,
-                                                ctx->copy_stream)
-                               : hipMemcpy2DAsync(dst, w, src, row_stride, w, nr,
-                                                  hipMemcpyHostToDevice, ctx->copy_stream);
-            // the chunk's flag: a 4-byte copy behind it on the same (copy-engine) queue --
-            // hipStreamWriteValue32 is a kernel launch per call on this runtime (~20 us each)
-            ctx->h_flags[c] = up.epoch;
-            if (e == hipSuccess)
-                e = hipMemcpyAsync(ctx->d_flags + c, ctx->h_flags + c, sizeof(uint32_t),
-                                   hipMemcpyHostToDevice, ctx->copy_stream);
-            if (e != hipSuccess) {
-                // the runtime cannot do this upload: this call takes one copy before the
-                // launch (counted; the caller's chunk setting stays)
-                (void)hipStreamSynchronize(ctx->copy_stream);
-                (void)hipGetLastError();
-                ++ctx->upload_fallbacks;
-                const uint32_t saved = ctx->chunks;
-                ctx->chunks = 1;
-                rc = run_host(ctx, data, n_frames, w, h, row_stride, frame_stride, cfg, rgb,
-                              offs, host_out);
-                ctx->chunks = saved;
-                return rc;
-            }
-        }
-    } else {
-        for (uint32_t f = 0; f < n_frames; ++f) {
-            const uint8_t* src = data + (size_t)f * frame_stride;
-            uint8_t* dst = stage + (size_t)f * frame_bytes * px;
-            hipError_t e = row_stride == px * w
-                               ? hipMemcpyAsync(dst, src, frame_bytes * px, hipMemcpyHostToDevice,
-                                                ctx->stream)
-                               : hipMemcpy2DAsync(dst, px * w, src, row_stride, px * w, h,
-                                                  hipMemcpyHostToDevice, ctx->stream);
-            if (e != hipSuccess) return FDF_ERR_DEVICE;
-        }
+    // fdf_fetch_last (detect_host).  A range that runs past its pinned mapping is copied, not
+    // read past its end.
+    const PinnedRange pin = probe_pinned(in.data, in.span());
+    const bool in_place = ctx->chunks == 0 && host_out && !rgb && n_frames == 1 && row_stride == w &&
+                          pin.kind == PinnedRange::kWhole && !(pin.flags & hipHostMallocCoherent);
+    if (pin.kind == PinnedRange::kPartial && (rc = pack_to_staging(ctx, &in))) return rc;
+    ChunkedUpload up;
+    if (!in_place && chunked) {
+        if (upload_chunked(ctx, in, nchunks, &up)) return retry_unchunked(ctx, in, cfg, offs, host_out);
+    } else if (!in_place) {
+        if ((rc = upload_frames(ctx, in, rgb ? ctx->d_rgb : ctx->d_in))) return rc;
     }
     // RGB: a luma pass, then the grey detector.  The detector with luma converted in its
     // loads (fdf_detect_device_rgb) is correct but measured 1.6x slower on 256 1080p frames:
@@ -741,8 +703,8 @@ int run_host(fdf_ctx* ctx, const uint8_t* data, uint32_t n_frames, uint32_t w, u
     if (rgb && fdfk::launch_rgb_to_luma(ctx->d_rgb, n_frames, (uint32_t)frame_bytes,
                                         3 * frame_bytes, ctx->d_in, ctx->stream) != hipSuccess)
         return FDF_ERR_DEVICE;
-    rc = enqueue(ctx, in_place ? in_place : ctx->d_in, n_frames, w, h, frame_bytes, cfg,
-                 out_dev, *out_cap, offs_dev, ctx->stream, false, up, in_place != nullptr);
+    rc = enqueue(ctx, in_place ? pin.dev : ctx->d_in, n_frames, w, h, frame_bytes, cfg, out.points(),
+                 out.cap(), out.offsets(), ctx->stream, false, up, in_place);
     if (chunked) {
         // the copies end before the detector does (it waits for the last one), but a failed
         // launch or a timed-out wait would leave them running: drain them before any return
@@ -750,31 +712,12 @@ int run_host(fdf_ctx* ctx, const uint8_t* data, uint32_t n_frames, uint32_t w, u
         if (!rc && e != hipSuccess) rc = FDF_ERR_DEVICE;
     }
     if (rc) return rc;
-    // the offsets on the host: read in place (host output) or copied back
-    auto fetch_offsets = [&]() -> hipError_t {
-        hipError_t e = hipSuccess;
-        if (!host_out)
-            e = hipMemcpyAsync(offs, offs_dev, sizeof(uint64_t) * (n_frames + 1ull),
-                               hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = sync_own_stream(ctx);
-        if (e == hipSuccess && host_out)
-            std::memcpy(offs, ctx->h_offs, sizeof(uint64_t) * (n_frames + 1ull));
-        return e;
-    };
-    if (fetch_offsets() != hipSuccess) return FDF_ERR_DEVICE;
+    if (fetch_offsets(ctx, offs, n_frames, host_out) != hipSuccess) return FDF_ERR_DEVICE;
     if (const uint32_t err = take_lookback_error(ctx)) {
         if (err & 4u) return FDF_ERR_DEVICE;   // a band never ran: nothing to rebuild from
-        if (err & 2u) {
-            // a band's wait for its upload chunk ran out (the copies are drained now): detect
-            // again from the whole frame, uploaded before the launch
-            ++ctx->upload_fallbacks;
-            const uint32_t saved = ctx->chunks;
-            ctx->chunks = 1;
-            rc = run_host(ctx, data, n_frames, w, h, row_stride, frame_stride, cfg, rgb, offs,
-                          host_out);
-            ctx->chunks = saved;
-            return rc;
-        }
+        // a band's wait for its upload chunk ran out (the copies are drained now): detect
+        // again from the whole frame, uploaded before the launch
+        if (err & 2u) return retry_unchunked(ctx, in, cfg, offs, host_out);
         // a direct-output band's look-back ran out (band_lookback): the offsets and points of
         // its frame on are not written; the slots and counts are, so the compaction rebuilds
         // both from them
@@ -782,23 +725,17 @@ int run_host(fdf_ctx* ctx, const uint8_t* data, uint32_t n_frames, uint32_t w, u
         fdfk::CompactParams c = ctx->last_compact;
         c.kp_stats = nullptr;
         c.group_sums = nullptr;
-        if (fdfk::launch_compact(c, ctx->stream) != hipSuccess || fetch_offsets() != hipSuccess)
+        if (fdfk::launch_compact(c, ctx->stream) != hipSuccess ||
+            fetch_offsets(ctx, offs, n_frames, host_out) != hipSuccess)
             return FDF_ERR_DEVICE;
     }
     const uint64_t total = offs[n_frames];
-    if (total > *out_cap) {
+    if (total > out.cap()) {
         // grow the output and compact again (the offsets do not change)
+        if ((rc = out.grow((size_t)total))) return rc;
         fdfk::CompactParams c = ctx->last_compact;
-        if (host_out) {
-            if ((rc = ensure_host(ctx, &ctx->h_out, &ctx->hd_out, &ctx->h_out_points, (size_t)total,
-                                  ctx->stream)))
-                return rc;
-            c.out = ctx->hd_out;
-        } else {
-            if ((rc = ensure(ctx, &ctx->d_out, &ctx->out_points, (size_t)total, ctx->stream))) return rc;
-            c.out = ctx->d_out;
-        }
-        c.cap = host_out ? ctx->h_out_points : ctx->out_points;
+        c.out = out.points();
+        c.cap = out.cap();
         c.kp_stats = nullptr;           // already reported (and reset) by the first compaction
         if (fdfk::launch_compact(c, ctx->stream) != hipSuccess ||
             note_done(ctx, ctx->stream) != hipSuccess)
@@ -814,7 +751,7 @@ int run_host(fdf_ctx* ctx, const uint8_t* data, uint32_t n_frames, uint32_t w, u
     ctx->last.height = h;
     ctx->last.cfg = *cfg;
     ctx->last.rgb = false;          // the luma frames are in d_in
-    ctx->last.in_place = in_place != nullptr;   // ... or were read in place (not in d_in)
+    ctx->last.in_place = in_place;  // ... or were read in place (not in d_in)
     return FDF_OK;
 }
 
@@ -1141,10 +1078,8 @@ int fdf_rgb_to_luma_device(fdf_ctx* ctx, const uint8_t* d_rgb, uint32_t n_frames
         n_frames > 65535u)
         return FDF_ERR_ARG;
     DeviceGuard guard(ctx->device);
-    if (fdfk::launch_rgb_to_luma(d_rgb, n_frames, (uint32_t)pixels, rgb_frame_stride_bytes, d_grey,
-                                 reinterpret_cast<hipStream_t>(stream)) != hipSuccess)
-        return FDF_ERR_DEVICE;
-    return FDF_OK;
+    return status_of(fdfk::launch_rgb_to_luma(d_rgb, n_frames, (uint32_t)pixels, rgb_frame_stride_bytes,
+                                              d_grey, reinterpret_cast<hipStream_t>(stream)));
 }
 
 int fdf_detect_scored(fdf_ctx* ctx, const uint8_t* data, uint32_t width, uint32_t height,
@@ -1178,15 +1113,12 @@ int fdf_score_device(fdf_ctx* ctx, const uint8_t* d_frames, uint32_t n_frames,
     if (!d_frames || !d_points || !d_scores || n_frames > 65535u) return FDF_ERR_ARG;
     if (n_frames > 1 && frame_stride_bytes < (uint64_t)width * height) return FDF_ERR_ARG;
     DeviceGuard guard(ctx->device);
-    const uint64_t fs = n_frames > 1 ? frame_stride_bytes : (uint64_t)width * height;
+    const uint64_t fs = frame_stride(n_frames, frame_stride_bytes, (uint64_t)width * height);
     const uint64_t est = std::min<uint64_t>(cap, (uint64_t)width * height / 32 * n_frames);
-    return fdfk::launch_score_frames(d_frames, width, fs, n_frames,
-                                     reinterpret_cast<const uint2*>(d_points), d_frame_offsets,
-                                     cap, score_blocks(est, n_frames), score_kind(cfg->nms),
-                                     cfg->threshold, cfg->count, d_scores,
-                                     reinterpret_cast<hipStream_t>(stream)) == hipSuccess
-               ? FDF_OK
-               : FDF_ERR_DEVICE;
+    return status_of(fdfk::launch_score_frames(
+        d_frames, width, fs, n_frames, reinterpret_cast<const uint2*>(d_points), d_frame_offsets, cap,
+        score_blocks(est, n_frames), score_kind(cfg->nms), cfg->threshold, cfg->count, d_scores,
+        reinterpret_cast<hipStream_t>(stream)));
 }
 
 int fdf_detect_batch(fdf_ctx* ctx, const uint8_t* data, uint32_t n_frames, uint32_t width,
@@ -1197,10 +1129,12 @@ int fdf_detect_batch(fdf_ctx* ctx, const uint8_t* data, uint32_t n_frames, uint3
                        cap, frame_offsets, n_out);
 }
 
-int fdf_detect_device(fdf_ctx* ctx, const uint8_t* d_frames, uint32_t n_frames,
-                      uint32_t width, uint32_t height, uint64_t frame_stride_bytes,
-                      const fdf_config* cfg, fdf_point* d_out, uint64_t cap,
-                      uint64_t* d_frame_offsets, void* stream) {
+// Shared body of fdf_detect_device and fdf_detect_device_rgb (`rgb`: RGB8 frames of 3 bytes
+// per pixel, luma converted in the detector's loads).
+static int detect_device(fdf_ctx* ctx, const uint8_t* d_frames, uint32_t n_frames, uint32_t width,
+                         uint32_t height, uint64_t frame_stride_bytes, const fdf_config* cfg,
+                         fdf_point* d_out, uint64_t cap, uint64_t* d_frame_offsets, void* stream,
+                         bool rgb) {
     if (!ctx || !d_frame_offsets) return FDF_ERR_ARG;
     int rc = check_config(cfg);
     if (rc) return rc;
@@ -1209,7 +1143,9 @@ int fdf_detect_device(fdf_ctx* ctx, const uint8_t* d_frames, uint32_t n_frames,
     if (rc) return rc;
     if (n_frames == 0) empty = 1;
     if (!empty && (!d_frames || (cap && !d_out))) return FDF_ERR_ARG;
-    if (n_frames > 1 && frame_stride_bytes < (uint64_t)width * height) return FDF_ERR_ARG;
+    const uint64_t fb = (rgb ? 3ull : 1ull) * width * height;
+    if (rgb && fb > 0x7fffffffull) return FDF_ERR_SIZE;
+    if (n_frames > 1 && frame_stride_bytes < fb) return FDF_ERR_ARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);   // NULL = the HIP null stream
     std::lock_guard<std::mutex> lock(ctx->mu);
     DeviceGuard guard(ctx->device);
@@ -1220,50 +1156,25 @@ int fdf_detect_device(fdf_ctx* ctx, const uint8_t* d_frames, uint32_t n_frames,
         ctx->pending_device_error = false;
         return FDF_ERR_DEVICE;
     }
-    if (empty) {
-        return hipMemsetAsync(d_frame_offsets, 0, sizeof(uint64_t) * (n_frames + 1ull), s) ==
-                       hipSuccess
-                   ? FDF_OK
-                   : FDF_ERR_DEVICE;
-    }
-    return enqueue(ctx, d_frames, n_frames, width, height,
-                   n_frames > 1 ? frame_stride_bytes : (uint64_t)width * height, cfg,
-                   reinterpret_cast<uint2*>(d_out), cap, d_frame_offsets, s);
+    if (empty) return status_of(hipMemsetAsync(d_frame_offsets, 0, sizeof(uint64_t) * (n_frames + 1ull), s));
+    return enqueue(ctx, d_frames, n_frames, width, height, frame_stride(n_frames, frame_stride_bytes, fb),
+                   cfg, reinterpret_cast<uint2*>(d_out), cap, d_frame_offsets, s, rgb);
+}
+
+int fdf_detect_device(fdf_ctx* ctx, const uint8_t* d_frames, uint32_t n_frames,
+                      uint32_t width, uint32_t height, uint64_t frame_stride_bytes,
+                      const fdf_config* cfg, fdf_point* d_out, uint64_t cap,
+                      uint64_t* d_frame_offsets, void* stream) {
+    return detect_device(ctx, d_frames, n_frames, width, height, frame_stride_bytes, cfg, d_out, cap,
+                         d_frame_offsets, stream, false);
 }
 
 int fdf_detect_device_rgb(fdf_ctx* ctx, const uint8_t* d_frames, uint32_t n_frames,
                           uint32_t width, uint32_t height, uint64_t frame_stride_bytes,
                           const fdf_config* cfg, fdf_point* d_out, uint64_t cap,
                           uint64_t* d_frame_offsets, void* stream) {
-    if (!ctx || !d_frame_offsets) return FDF_ERR_ARG;
-    int rc = check_config(cfg);
-    if (rc) return rc;
-    int empty = 0;
-    rc = check_shape(width, height, &empty);
-    if (rc) return rc;
-    if (n_frames == 0) empty = 1;
-    if (!empty && (!d_frames || (cap && !d_out))) return FDF_ERR_ARG;
-    const uint64_t fb = 3ull * width * height;
-    if (fb > 0x7fffffffull) return FDF_ERR_SIZE;
-    if (n_frames > 1 && frame_stride_bytes < fb) return FDF_ERR_ARG;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard guard(ctx->device);
-    // an earlier asynchronous direct-output launch of this context had a look-back wait run
-    // out (band_lookback; never seen in practice): its output was incomplete -- reported once
-    // (also when a host call in between found the error word first: pending_device_error)
-    if (take_lookback_error(ctx) || ctx->pending_device_error) {
-        ctx->pending_device_error = false;
-        return FDF_ERR_DEVICE;
-    }
-    if (empty) {
-        return hipMemsetAsync(d_frame_offsets, 0, sizeof(uint64_t) * (n_frames + 1ull), s) ==
-                       hipSuccess
-                   ? FDF_OK
-                   : FDF_ERR_DEVICE;
-    }
-    return enqueue(ctx, d_frames, n_frames, width, height, n_frames > 1 ? frame_stride_bytes : fb,
-                   cfg, reinterpret_cast<uint2*>(d_out), cap, d_frame_offsets, s, true);
+    return detect_device(ctx, d_frames, n_frames, width, height, frame_stride_bytes, cfg, d_out, cap,
+                         d_frame_offsets, stream, true);
 }
 
 int fdf_score_points(fdf_ctx* ctx, const uint8_t* data, uint32_t width, uint32_t height,
@@ -1289,10 +1200,7 @@ int fdf_score_points(fdf_ctx* ctx, const uint8_t* data, uint32_t width, uint32_t
     if ((rc = ensure(ctx, &ctx->d_out, &ctx->out_points, n_points + (n_points + 3) / 4,
                      ctx->stream)))
         return rc;
-    hipError_t e = stride_bytes == width
-                       ? hipMemcpyAsync(ctx->d_in, data, frame_bytes, hipMemcpyHostToDevice, ctx->stream)
-                       : hipMemcpy2DAsync(ctx->d_in, width, data, stride_bytes, width, height,
-                                          hipMemcpyHostToDevice, ctx->stream);
+    hipError_t e = upload_rows(ctx->d_in, data, stride_bytes, width, height, ctx->stream);
     if (e == hipSuccess)
         e = hipMemcpyAsync(ctx->d_out, points, n_points * sizeof(fdf_point), hipMemcpyHostToDevice,
                            ctx->stream);

@@ -153,4 +153,28 @@ inline int check_shape(uint32_t w, uint32_t h, int* empty) {
 
 inline uint64_t align256(uint64_t v) { return (v + 255u) & ~255ull; }
 
+// Frames of a _device entry lie `stride_bytes` apart; a single frame's stride is not looked at.
+inline uint64_t frame_stride(uint32_t n_frames, uint64_t stride_bytes, uint64_t frame_bytes) {
+    return n_frames > 1 ? stride_bytes : frame_bytes;
+}
+
+inline int status_of(hipError_t e) { return e == hipSuccess ? FDF_OK : FDF_ERR_DEVICE; }
+
+// `rows` host rows of `row_bytes` bytes, `stride_bytes` apart, to a packed device buffer (one
+// plain copy when the host rows are packed too), and the way back.
+inline hipError_t upload_rows(void* dst, const void* src, size_t stride_bytes, size_t row_bytes,
+                              size_t rows, hipStream_t stream) {
+    return stride_bytes == row_bytes
+               ? hipMemcpyAsync(dst, src, row_bytes * rows, hipMemcpyHostToDevice, stream)
+               : hipMemcpy2DAsync(dst, row_bytes, src, stride_bytes, row_bytes, rows,
+                                  hipMemcpyHostToDevice, stream);
+}
+inline hipError_t download_rows(void* dst, size_t stride_bytes, const void* src, size_t row_bytes,
+                                size_t rows, hipStream_t stream) {
+    return stride_bytes == row_bytes
+               ? hipMemcpyAsync(dst, src, row_bytes * rows, hipMemcpyDeviceToHost, stream)
+               : hipMemcpy2DAsync(dst, stride_bytes, src, row_bytes, row_bytes, rows,
+                                  hipMemcpyDeviceToHost, stream);
+}
+
 }  // namespace

@@ -52,20 +52,12 @@ public:
     // a frame whose rows lie `stride_bytes` apart, packed on the device
     void upload_frame(Part<uint8_t> p, const uint8_t* data, uint32_t width, uint32_t height,
                       size_t stride_bytes) {
-        if (!ok()) return;
-        e_ = stride_bytes == width
-                 ? hipMemcpyAsync(at(p), data, p.count, hipMemcpyHostToDevice, ctx_->stream)
-                 : hipMemcpy2DAsync(at(p), width, data, stride_bytes, width, height,
-                                    hipMemcpyHostToDevice, ctx_->stream);
+        if (ok()) e_ = upload_rows(at(p), data, stride_bytes, width, height, ctx_->stream);
     }
     // a packed device frame to rows `stride_bytes` apart
     void download_frame(uint8_t* out, Part<uint8_t> p, uint32_t width, uint32_t height,
                         size_t stride_bytes) {
-        if (!ok()) return;
-        e_ = stride_bytes == width
-                 ? hipMemcpyAsync(out, at(p), p.count, hipMemcpyDeviceToHost, ctx_->stream)
-                 : hipMemcpy2DAsync(out, stride_bytes, at(p), width, width, height,
-                                    hipMemcpyDeviceToHost, ctx_->stream);
+        if (ok()) e_ = download_rows(out, stride_bytes, at(p), width, height, ctx_->stream);
     }
     void upload_one_frame(Part<uint64_t> p, uint64_t n_points) {    // offsets {0, n_points}
         one_frame_[1] = n_points;
@@ -98,11 +90,6 @@ bool points_inside(const fdf_point* points, size_t n_points, uint32_t width, uin
     return true;
 }
 
-// Frames of a _device entry lie `stride_bytes` apart; a single frame's stride is not looked at.
-inline uint64_t frame_stride(uint32_t n_frames, uint64_t stride_bytes, uint64_t frame_bytes) {
-    return n_frames > 1 ? stride_bytes : frame_bytes;
-}
-
 // What fdf_orient_device and fdf_describe_device check after their own parameters.  *todo is
 // clear when the call is valid and has nothing to enqueue; otherwise *stride is the frames'.
 inline int check_point_frames(uint32_t n_frames, uint32_t width, uint32_t height, uint64_t cap,
@@ -127,8 +114,6 @@ inline uint32_t chunks_per_frame(uint64_t cap, uint32_t n_frames, uint32_t width
     const uint64_t est = std::min<uint64_t>(cap, (uint64_t)width * height / 32 * n_frames);
     return (uint32_t)std::min<uint64_t>(max_chunks, est / n_frames / per_wg + 1);
 }
-
-inline int status_of(hipError_t e) { return e == hipSuccess ? FDF_OK : FDF_ERR_DEVICE; }
 
 }  // namespace
 
