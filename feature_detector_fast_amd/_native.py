@@ -48,6 +48,7 @@ EXPORTED_SYMBOLS = (
     "fdf_resize_frame", "fdf_pyramid_plan", "fdf_pyramid_taps", "fdf_pyramid_device",
     "fdf_harris_codes", "fdf_harris_device", "fdf_harris_points", "fdf_ransac_sample",
     "fdf_ransac_scratch_bytes", "fdf_ransac_device", "fdf_ransac_points",
+    "fdf_refine_scratch_bytes", "fdf_refine_device", "fdf_refine_points",
 )
 
 
@@ -278,6 +279,14 @@ def load():
     lib.fdf_ransac_points.restype = ctypes.c_int
     lib.fdf_ransac_points.argtypes = [vp, vp, vp, sz, sz, vp, vp, u32, u32, u32, ctypes.c_float,
                                       u32, vp, vp]
+    lib.fdf_refine_scratch_bytes.restype = ctypes.c_int
+    lib.fdf_refine_scratch_bytes.argtypes = [u32, u64, ctypes.POINTER(u64)]
+    lib.fdf_refine_device.restype = ctypes.c_int
+    lib.fdf_refine_device.argtypes = [vp, u32, vp, vp, u64, vp, vp, vp, u64, vp, u32, u32, vp,
+                                      ctypes.c_float, u32, vp, vp, vp, vp, u64, vp]
+    lib.fdf_refine_points.restype = ctypes.c_int
+    lib.fdf_refine_points.argtypes = [vp, vp, vp, sz, sz, vp, vp, u32, u32, vp, ctypes.c_float,
+                                      u32, vp, vp, vp]
     del u8p
     _lib = lib
     return lib

@@ -483,4 +483,17 @@ struct RansacParams {
 // compaction, hypothesis and finalisation kernels on `stream`
 hipError_t launch_ransac(const RansacParams& p, hipStream_t stream);
 
+// Least-squares refinement of the models over their inliers (fdf_ransac.hip; fdf_refine_device).
+constexpr uint32_t kRefineMaxRounds = 8;
+struct RefineParams {
+    RansacParams r;              // the correspondences; tt: the refinement's threshold; models:
+                                 // the output (may be models_in); inliers; corr and n_corr: this
+                                 // stage's scratch; n_hyp, seed and counts are unused
+    const double* models_in;     // n_frames fdf_model
+    uint32_t* rounds;            // n_frames accepted rounds, or NULL
+    uint32_t n_rounds;           // 0..kRefineMaxRounds
+};
+// compaction and refinement kernels on `stream`
+hipError_t launch_refine(const RefineParams& p, hipStream_t stream);
+
 }  // namespace fdfk

@@ -32,6 +32,16 @@
 // inlier bytes of the frame's queries t, t + 256, ... from the original arrays: one store per
 // byte of the range, none outside.
 //
+// refine_kernel<S> (fdf_refine_device: the compaction kernel again, then this one).  One
+// workgroup per frame refits the frame's model over its inliers by least squares, all rounds
+// inside the workgroup.  A round is four passes over the frame's compacted correspondences,
+// thread t taking j = t, t + 256, ...: the inliers' count and coordinate sums, their mean absolute
+// deviations, the 28 (affine: 11) different sums of the normalised normal equations, and the
+// count under the new model.  Each pass ends in refine_sum: the 256 lane sums of every quantity
+// fold through LDS in the fixed halving order (28 x 256 doubles: 56 KB), the additions of a step
+// spread over the workgroup, and every thread reads the totals back and solves redundantly with
+// the shared elimination.  Every branch depends on those totals alone, so it is uniform.
+//
 // The whole file is compiled without floating-point contraction: a - b * c stays v_mul_f64 +
 // v_add_f64, as numpy computes it; `/` is the correctly rounded v_div_scale / v_div_fmas /
 // v_div_fixup sequence.
@@ -102,26 +112,14 @@ __global__ __launch_bounds__(kRansacFrameThreads) void ransac_compact_kernel(Ran
     if (tid == 0) P.n_corr[f] = base;
 }
 
-// The model of the sample `c` (S = 3: affine, 4: homography) by Gaussian elimination with
-// partial pivoting and back substitution, every operation as include/fdf.h writes it.  False:
-// a pivot below 2^-20 (or no pivot that is a number).  Everything is unrolled; rows are swapped
-// by selects on the run-time pivot row.
-template <int S>
-__device__ __forceinline__ bool ransac_fit(const Corr (&c)[S], double (&h)[9]) {
-    constexpr int N = 2 * S;
+// Solves the N x N system A h = b by Gaussian elimination with partial pivoting and back
+// substitution, every operation as include/fdf.h writes it; h[N..8) = 0 and h[8] = 1.  False: a
+// pivot below 2^-20 (or no pivot that is a number).  Everything is unrolled; rows are swapped by
+// selects on the run-time pivot row.  fill(A, b) writes the system into the solver's own arrays.
+template <int N, typename Fill>
+__device__ __forceinline__ bool ransac_solve(Fill fill, double (&h)[9]) {
     double A[N][N], b[N];
-#pragma unroll
-    for (int k = 0; k < S; ++k) {
-        const double row0[8] = {c[k].x, c[k].y, 1.0, 0.0, 0.0, 0.0, -(c[k].u * c[k].x), -(c[k].u * c[k].y)};
-        const double row1[8] = {0.0, 0.0, 0.0, c[k].x, c[k].y, 1.0, -(c[k].v * c[k].x), -(c[k].v * c[k].y)};
-#pragma unroll
-        for (int j = 0; j < N; ++j) {
-            A[2 * k][j] = row0[j];
-            A[2 * k + 1][j] = row1[j];
-        }
-        b[2 * k] = c[k].u;
-        b[2 * k + 1] = c[k].v;
-    }
+    fill(A, b);
     bool valid = true;
 #pragma unroll
     for (int col = 0; col < N; ++col) {
@@ -168,6 +166,26 @@ __device__ __forceinline__ bool ransac_fit(const Corr (&c)[S], double (&h)[9]) {
         h[i] = t / A[i][i];
     }
     return valid;
+}
+
+// The model of the sample `c` (S = 3: affine, 4: homography): its 2 S rows, solved.
+template <int S>
+__device__ __forceinline__ bool ransac_fit(const Corr (&c)[S], double (&h)[9]) {
+    constexpr int N = 2 * S;
+    return ransac_solve<N>([&c](double (&A)[N][N], double (&b)[N]) {
+#pragma unroll
+        for (int k = 0; k < S; ++k) {
+            const double row0[8] = {c[k].x, c[k].y, 1.0, 0.0, 0.0, 0.0, -(c[k].u * c[k].x), -(c[k].u * c[k].y)};
+            const double row1[8] = {0.0, 0.0, 0.0, c[k].x, c[k].y, 1.0, -(c[k].v * c[k].x), -(c[k].v * c[k].y)};
+#pragma unroll
+            for (int j = 0; j < N; ++j) {
+                A[2 * k][j] = row0[j];
+                A[2 * k + 1][j] = row1[j];
+            }
+            b[2 * k] = c[k].u;
+            b[2 * k + 1] = c[k].v;
+        }
+    }, h);
 }
 
 // Forward transfer error of at most T pixels, without a division; false for any NaN.
@@ -305,7 +323,286 @@ __global__ __launch_bounds__(kRansacFrameThreads) void ransac_finalise_kernel(Ra
     }
 }
 
+// ---- least-squares refinement of a model over its inliers (fdf_refine_device) -----------------
+
+constexpr double kRefineInf = __builtin_huge_val();
+
+// The frame's sums of K quantities in include/fdf.h's fixed order: acc[k] is this thread's lane
+// sum (correspondence j belongs to lane j mod 256); the 256 lane sums fold as
+// sum[t] = sum[t] + sum[t + step] for step = 128 .. 1, the K x step additions of a step spread
+// over the workgroup.  Every thread leaves with the K totals.
+template <int K>
+__device__ __forceinline__ void refine_sum(double (&acc)[K], double (*s)[kRansacFrameThreads],
+                                           uint32_t tid) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) s[k][tid] = acc[k];
+    __syncthreads();
+    for (uint32_t step = kRansacFrameThreads / 2; step > 0; step /= 2) {
+        const uint32_t shift = 31u - (uint32_t)__builtin_clz(step);
+        for (uint32_t e = tid; e < (uint32_t)K * step; e += kRansacFrameThreads) {
+            const uint32_t k = e >> shift, t = e & (step - 1u);
+            s[k][t] = s[k][t] + s[k][t + step];
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) acc[k] = s[k][0];
+    __syncthreads();                                          // the next sum rewrites s
+}
+
+__device__ __forceinline__ Corr refine_load(const double* corr, uint64_t j) {
+    const double2* src = reinterpret_cast<const double2*>(corr + 4 * j);
+    const double2 a = src[0], b = src[1];
+    return Corr{a.x, a.y, b.x, b.y};
+}
+
+// a[0..5) = the inliers of `h` among the m correspondences: their number, sum x, y, u, v.
+__device__ __forceinline__ void refine_score(const double (&h)[9], const double* corr, uint32_t m,
+                                             double tt, double (*s)[kRansacFrameThreads],
+                                             uint32_t tid, double (&a)[5]) {
+#pragma unroll
+    for (int k = 0; k < 5; ++k) a[k] = 0.0;
+    for (uint64_t j = tid; j < m; j += kRansacFrameThreads) {
+        const Corr c = refine_load(corr, j);
+        const bool in = ransac_inlier(h, c.x, c.y, c.u, c.v, tt);
+        a[0] = a[0] + (in ? 1.0 : 0.0);
+        a[1] = a[1] + (in ? c.x : 0.0);
+        a[2] = a[2] + (in ? c.y : 0.0);
+        a[3] = a[3] + (in ? c.u : 0.0);
+        a[4] = a[4] + (in ? c.v : 0.0);
+    }
+    refine_sum<5>(a, s, tid);
+}
+
+// The sums of the normal equations that differ (S = 4: 28, S = 3: 11), with a = (X, Y, 1),
+// p = (-(U X), -(U Y)) and q = (-(V X), -(V Y)) the tails of a correspondence's two rows:
+//   0..4    XX XY X YY Y        G[i][j] = G[3 + i][3 + j], i <= j < 3 (G[2][2] = n)
+//   5..10   XU YU U XV YV V     g[0..6)
+//   11..16  X p0, X p1, Y p0, Y p1, p0, p1      G[0..3)[6..8)
+//   17..22  X q0, X q1, Y q0, Y q1, q0, q1      G[3..6)[6..8)
+//   23..25  p0 p0 + q0 q0, p0 p1 + q0 q1, p1 p1 + q1 q1      G[6][6], G[6][7], G[7][7]
+//   26..27  p0 U + q0 V, p1 U + q1 V            g[6], g[7]
+template <int S>
+constexpr int kRefineSums = S == 4 ? 28 : 11;
+
+// One refit of `h` over its inliers: normalise, accumulate, solve, denormalise into `out`.
+// False: the round failed (include/fdf.h).  n and the sums a[1..5) are refine_score's of `h`.
+// Uniform over the workgroup: every value a branch depends on comes out of refine_sum.
+template <int S>
+__device__ __forceinline__ bool refine_round(const double (&h)[9], const double (&a)[5],
+                                             const double* corr, uint32_t m, double tt,
+                                             double (*s)[kRansacFrameThreads], uint32_t tid,
+                                             double (&out)[9]) {
+    constexpr int N = 2 * S, K = kRefineSums<S>;
+    const double n = a[0];
+    const double cx = a[1] / n, cy = a[2] / n, cu = a[3] / n, cv = a[4] / n;
+    double d[2] = {0.0, 0.0};
+    for (uint64_t j = tid; j < m; j += kRansacFrameThreads) {
+        const Corr c = refine_load(corr, j);
+        const bool in = ransac_inlier(h, c.x, c.y, c.u, c.v, tt);
+        const double dq = __builtin_fabs(c.x - cx) + __builtin_fabs(c.y - cy);
+        const double dt = __builtin_fabs(c.u - cu) + __builtin_fabs(c.v - cv);
+        d[0] = d[0] + (in ? dq : 0.0);
+        d[1] = d[1] + (in ? dt : 0.0);
+    }
+    refine_sum<2>(d, s, tid);
+    if (!(n >= (double)S && d[0] > 0.0 && d[0] < kRefineInf && d[1] > 0.0 && d[1] < kRefineInf))
+        return false;
+    const double sq = (n + n) / d[0], st = (n + n) / d[1];
+
+    double g[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) g[k] = 0.0;
+    for (uint64_t j = tid; j < m; j += kRansacFrameThreads) {
+        const Corr c = refine_load(corr, j);
+        const bool in = ransac_inlier(h, c.x, c.y, c.u, c.v, tt);
+        const double X = (c.x - cx) * sq, Y = (c.y - cy) * sq;
+        const double U = (c.u - cu) * st, V = (c.v - cv) * st;
+        double term[K];
+        term[0] = X * X;
+        term[1] = X * Y;
+        term[2] = X;
+        term[3] = Y * Y;
+        term[4] = Y;
+        term[5] = X * U;
+        term[6] = Y * U;
+        term[7] = U;
+        term[8] = X * V;
+        term[9] = Y * V;
+        term[10] = V;
+        if constexpr (S == 4) {
+            const double p0 = -(U * X), p1 = -(U * Y), q0 = -(V * X), q1 = -(V * Y);
+            term[11] = X * p0;
+            term[12] = X * p1;
+            term[13] = Y * p0;
+            term[14] = Y * p1;
+            term[15] = p0;
+            term[16] = p1;
+            term[17] = X * q0;
+            term[18] = X * q1;
+            term[19] = Y * q0;
+            term[20] = Y * q1;
+            term[21] = q0;
+            term[22] = q1;
+            term[23] = p0 * p0 + q0 * q0;
+            term[24] = p0 * p1 + q0 * q1;
+            term[25] = p1 * p1 + q1 * q1;
+            term[26] = p0 * U + q0 * V;
+            term[27] = p1 * U + q1 * V;
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k) g[k] = g[k] + (in ? term[k] : 0.0);
+    }
+    refine_sum<K>(g, s, tid);
+
+    double hn[9];
+    const bool solved = ransac_solve<N>([&g, n](double (&G)[N][N], double (&b)[N]) {
+#pragma unroll
+        for (int i = 0; i < N; ++i)
+#pragma unroll
+            for (int j = 0; j < N; ++j) G[i][j] = 0.0;
+        const double aa[3][3] = {{g[0], g[1], g[2]}, {g[1], g[3], g[4]}, {g[2], g[4], n}};
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                G[i][j] = aa[i][j];
+                G[3 + i][3 + j] = aa[i][j];
+            }
+            b[i] = g[5 + i];
+            b[3 + i] = g[8 + i];
+        }
+        if constexpr (S == 4) {
+#pragma unroll
+            for (int i = 0; i < 6; ++i) {
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    G[i][6 + j] = g[11 + 2 * i + j];
+                    G[6 + j][i] = g[11 + 2 * i + j];
+                }
+            }
+            G[6][6] = g[23];
+            G[6][7] = g[24];
+            G[7][6] = g[24];
+            G[7][7] = g[25];
+            b[6] = g[26];
+            b[7] = g[27];
+        }
+    }, hn);
+
+    // H = T2^-1 Hn T1, then / H[8]
+    double A[3][3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        A[r][0] = hn[3 * r] * sq;
+        A[r][1] = hn[3 * r + 1] * sq;
+        A[r][2] = (hn[3 * r + 2] - A[r][0] * cx) - A[r][1] * cy;
+    }
+    bool ok = solved;
+    if constexpr (S == 4) {
+        double H[9];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            H[c] = A[0][c] / st + cu * A[2][c];
+            H[3 + c] = A[1][c] / st + cv * A[2][c];
+            H[6 + c] = A[2][c];
+        }
+        const double w = __builtin_fabs(H[8]);
+        ok = ok && w >= kRansacMinPivot && w < kRefineInf;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) out[k] = H[k] / H[8];
+    } else {
+        out[0] = A[0][0] / st;
+        out[1] = A[0][1] / st;
+        out[2] = A[0][2] / st + cu;
+        out[3] = A[1][0] / st;
+        out[4] = A[1][1] / st;
+        out[5] = A[1][2] / st + cv;
+        out[6] = 0.0;
+        out[7] = 0.0;
+    }
+    out[8] = 1.0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) ok = ok && __builtin_fabs(out[k]) < kRefineInf;
+    return ok;
+}
+
+// One workgroup per frame; all rounds inside it.  The correspondences are the compaction
+// kernel's, in the stage's own scratch; the inlier bytes come from the original arrays as in the
+// finalise kernel.
+template <int S>
+__global__ __launch_bounds__(kRansacFrameThreads) void refine_kernel(RefineParams R) {
+    __shared__ double s_sum[kRefineSums<S>][kRansacFrameThreads];
+    const RansacParams& P = R.r;
+    const uint32_t f = blockIdx.x, tid = threadIdx.x;
+    const IndexRange qr = frame_range(P.q_offs, P.q_cap, f);
+    const IndexRange tr = frame_range(P.t_offs, P.t_cap, f);
+    const uint32_t m = min(P.n_corr[f], (uint32_t)min(qr.hi - qr.lo, (uint64_t)kMatchMaxCap));
+    const double* corr = P.corr + 4 * qr.lo;
+
+    const double* in = R.models_in + 11 * (uint64_t)f;
+    double h[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) h[k] = in[k];
+    const uint2* in_tail = reinterpret_cast<const uint2*>(in + 9);
+    const uint2 tail0 = in_tail[0], tail1 = in_tail[1];       // n_corr, n_inliers; hypothesis, n_valid
+    __syncthreads();                                          // models_out may be models_in
+    const bool have = tail1.x != kRansacInvalid;              // uniform
+
+    uint32_t count = 0, rounds = 0;
+    if (have) {
+        double a[5];
+        refine_score(h, corr, m, P.tt, s_sum, tid, a);
+        count = (uint32_t)a[0];
+        for (uint32_t r = 0; r < R.n_rounds; ++r) {
+            double h2[9], a2[5];
+            if (!refine_round<S>(h, a, corr, m, P.tt, s_sum, tid, h2)) break;
+            refine_score(h2, corr, m, P.tt, s_sum, tid, a2);
+            const uint32_t count2 = (uint32_t)a2[0];
+            if (count2 < count) break;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) h[k] = h2[k];
+#pragma unroll
+            for (int k = 0; k < 5; ++k) a[k] = a2[k];
+            count = count2;
+            ++rounds;
+        }
+    }
+    if (tid == 0) {
+        double* out = P.models + 11 * (uint64_t)f;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) out[k] = h[k];
+        uint2* tail = reinterpret_cast<uint2*>(out + 9);
+        tail[0] = have ? make_uint2(m, count) : tail0;
+        tail[1] = tail1;
+        if (R.rounds) R.rounds[f] = rounds;
+    }
+    if (P.inliers) {
+        for (uint64_t i = qr.lo + tid; i < qr.hi; i += kRansacFrameThreads) {
+            Corr c{0.0, 0.0, 0.0, 0.0};
+            const bool is = correspondence(P, i, tr, &c) && have &&
+                            ransac_inlier(h, c.x, c.y, c.u, c.v, P.tt);
+            P.inliers[i] = is ? 1u : 0u;
+        }
+    }
+}
+
 }  // namespace
+
+hipError_t launch_refine(const RefineParams& p, hipStream_t stream) {
+    const RansacParams& r = p.r;
+    if (r.n_frames == 0) return hipSuccess;
+    if (r.n_frames > 65535u || r.q_cap > kMatchMaxCap || r.t_cap > kMatchMaxCap ||
+        r.model > kRansacHomography || r.coords > kRansacF32 || p.n_rounds > kRefineMaxRounds)
+        return hipErrorInvalidValue;
+    const dim3 frames(r.n_frames), block(kRansacFrameThreads);
+    hipLaunchKernelGGL(ransac_compact_kernel, frames, block, 0, stream, r);
+    if (r.model == kRansacAffine)
+        hipLaunchKernelGGL(refine_kernel<3>, frames, block, 0, stream, p);
+    else
+        hipLaunchKernelGGL(refine_kernel<4>, frames, block, 0, stream, p);
+    return hipGetLastError();
+}
 
 hipError_t launch_ransac(const RansacParams& p, hipStream_t stream) {
     if (p.n_frames == 0) return hipSuccess;

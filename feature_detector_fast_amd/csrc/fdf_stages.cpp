@@ -1086,4 +1086,115 @@ int fdf_ransac_points(fdf_ctx* ctx, const void* q_coords, const void* t_coords, 
     return a.close();
 }
 
+// ---- least-squares refinement of the models over their inliers (fdf_ransac.hip) ---------------
+namespace {
+
+// Scratch of one fdf_refine_device call: RansacLayout's first two parts.
+int refine_layout(uint32_t n_frames, uint64_t q_cap, RansacLayout* L) {
+    const int rc = ransac_layout(n_frames, q_cap, 1, L);
+    if (rc == FDF_OK) L->total = L->counts;
+    return rc;
+}
+
+}  // namespace
+
+int fdf_refine_scratch_bytes(uint32_t n_frames, uint64_t q_cap, uint64_t* bytes) {
+    if (!bytes) return FDF_ERR_ARG;
+    RansacLayout L;
+    const int rc = refine_layout(n_frames, q_cap, &L);
+    if (rc) return rc;
+    *bytes = L.total;
+    return FDF_OK;
+}
+
+int fdf_refine_device(fdf_ctx* ctx, uint32_t n_frames, const fdf_match* d_matches,
+                      const uint8_t* d_keep, uint64_t q_cap, const uint64_t* d_q_offsets,
+                      const void* d_q_coords, const void* d_t_coords, uint64_t t_cap,
+                      const uint64_t* d_t_offsets, uint32_t coords, uint32_t model,
+                      const fdf_model* d_models_in, float threshold, uint32_t n_rounds,
+                      fdf_model* d_models_out, uint8_t* d_inliers, uint32_t* d_rounds,
+                      void* d_scratch, uint64_t scratch_bytes, void* stream) {
+    RansacLayout L;
+    if (!ctx || refine_layout(n_frames, q_cap, &L) != FDF_OK || t_cap > fdfk::kMatchMaxCap ||
+        !ransac_values_ok(coords, model, threshold) || n_rounds > fdfk::kRefineMaxRounds)
+        return FDF_ERR_ARG;
+    if (n_frames == 0) return FDF_OK;
+    if (!d_matches || !d_q_offsets || !d_t_offsets || !d_q_coords || !d_t_coords || !d_models_in ||
+        !d_models_out || !d_scratch || scratch_bytes < L.total ||
+        ((uintptr_t)d_matches & 7u) != 0 || ((uintptr_t)d_q_coords & 7u) != 0 ||
+        ((uintptr_t)d_t_coords & 7u) != 0 || ((uintptr_t)d_models_in & 7u) != 0 ||
+        ((uintptr_t)d_models_out & 7u) != 0 || ((uintptr_t)d_rounds & 3u) != 0 ||
+        ((uintptr_t)d_scratch & 255u) != 0)
+        return FDF_ERR_ARG;
+    uint8_t* base = static_cast<uint8_t*>(d_scratch);
+    fdfk::RefineParams p{};
+    p.r.matches = reinterpret_cast<const uint2*>(d_matches);
+    p.r.keep = d_keep;
+    p.r.q_offs = d_q_offsets;
+    p.r.q_cap = q_cap;
+    p.r.q_coords = static_cast<const uint2*>(d_q_coords);
+    p.r.t_coords = static_cast<const uint2*>(d_t_coords);
+    p.r.t_offs = d_t_offsets;
+    p.r.t_cap = t_cap;
+    p.r.n_frames = n_frames;
+    p.r.coords = coords;
+    p.r.model = model;
+    p.r.tt = (double)threshold * (double)threshold;
+    p.r.models = reinterpret_cast<double*>(d_models_out);
+    p.r.inliers = d_inliers;
+    p.r.corr = reinterpret_cast<double*>(base + L.corr);
+    p.r.n_corr = reinterpret_cast<uint32_t*>(base + L.n_corr);
+    p.models_in = reinterpret_cast<const double*>(d_models_in);
+    p.rounds = d_rounds;
+    p.n_rounds = n_rounds;
+    DeviceGuard guard(ctx->device);
+    return status_of(fdfk::launch_refine(p, reinterpret_cast<hipStream_t>(stream)));
+}
+
+int fdf_refine_points(fdf_ctx* ctx, const void* q_coords, const void* t_coords, size_t n_q,
+                      size_t n_t, const fdf_match* matches, const uint8_t* keep, uint32_t coords,
+                      uint32_t model, const fdf_model* model_in, float threshold,
+                      uint32_t n_rounds, fdf_model* model_out, uint8_t* inliers_out,
+                      uint32_t* rounds_out) {
+    RansacLayout L;
+    if (!ctx || !model_in || !model_out || refine_layout(1, n_q, &L) != FDF_OK ||
+        n_t > fdfk::kMatchMaxCap || !ransac_values_ok(coords, model, threshold) ||
+        n_rounds > fdfk::kRefineMaxRounds)
+        return FDF_ERR_ARG;
+    if (n_q && (!q_coords || !matches)) return FDF_ERR_ARG;
+    if (n_t && !t_coords) return FDF_ERR_ARG;
+    const uint64_t t_offs[2] = {0, n_t};                  // an asynchronous copy's source
+    Arena a(ctx);
+    const auto d_q = a.part<fdf_point>(n_q);
+    const auto d_t = a.part<fdf_point>(n_t);
+    const auto d_m = a.part<fdf_match>(n_q);
+    const auto d_keep = a.part<uint8_t>(keep ? n_q : 0);
+    const auto d_qo = a.part<uint64_t>(2);
+    const auto d_to = a.part<uint64_t>(2);
+    const auto d_model = a.part<fdf_model>(1);
+    const auto d_rounds = a.part<uint32_t>(1);
+    const auto d_in = a.part<uint8_t>(inliers_out ? n_q : 0);
+    const auto d_scratch = a.part<uint8_t>(L.total);
+    if (a.open() != FDF_OK) return FDF_ERR_ALLOC;
+    if (n_q) a.upload(d_q, static_cast<const fdf_point*>(q_coords));
+    if (n_t) a.upload(d_t, static_cast<const fdf_point*>(t_coords));
+    if (n_q) a.upload(d_m, matches);
+    if (keep && n_q) a.upload(d_keep, keep);
+    a.upload_one_frame(d_qo, n_q);
+    a.upload(d_to, t_offs);
+    a.upload(d_model, model_in);
+    if (a.ok()) {
+        const int status = fdf_refine_device(
+            ctx, 1, a.at(d_m), keep ? a.at(d_keep) : nullptr, n_q, a.at(d_qo), a.at(d_q),
+            a.at(d_t), n_t, a.at(d_to), coords, model, a.at(d_model), threshold, n_rounds,
+            a.at(d_model), inliers_out ? a.at(d_in) : nullptr, a.at(d_rounds), a.at(d_scratch),
+            L.total, ctx->stream);
+        if (status != FDF_OK) return status;
+    }
+    a.download(model_out, d_model, 1);
+    if (rounds_out) a.download(rounds_out, d_rounds, 1);
+    if (inliers_out && n_q) a.download(inliers_out, d_in, n_q);
+    return a.close();
+}
+
 }  // extern "C"

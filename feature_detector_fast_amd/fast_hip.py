@@ -1582,6 +1582,7 @@ MODEL_DTYPE = np.dtype([("h", "<f8", (9,)), ("n_corr", "<u4"), ("n_inliers", "<u
 RANSAC_NONE = _native.FDF_RANSAC_NONE
 _MODELS = {"affine": _native.FDF_MODEL_AFFINE, "homography": _native.FDF_MODEL_HOMOGRAPHY}
 _RANSAC_MAX_HYP = 65536
+_REFINE_MAX_ROUNDS = 8
 
 
 def _ransac_model(model):
@@ -1730,13 +1731,8 @@ def _host_matches(matches, n):
     return rec
 
 
-def estimate_model(q_points, t_points, matches, keep=None, model="homography", n_hyp=256,
-                   threshold=3.0, seed=0, device=0):
-    """RANSAC estimation of the affine map or homography that takes the query points to their
-    matches (fdf_ransac_points): (H as a (3, 3) float64 array or None when there is no model, the
-    (n_q,) bool inlier mask, the MODEL_DTYPE record).  ``q_points`` (n_q, 2) and ``t_points``
-    (n_t, 2) are both integer or both float32 arrays of (x, y); ``matches`` is match_descriptors'
-    result (or (n_q,) train indices, negative = none), ``keep`` an optional (n_q,) mask."""
+def _host_pair(q_points, t_points, matches, keep):
+    """The host sets of estimate_model and refine_model: (q, t, FDF_COORDS_*, records, keep)."""
     q, kind = _host_coords(q_points, "q_points")
     t, t_kind = _host_coords(t_points, "t_points")
     if kind != t_kind:
@@ -1746,8 +1742,45 @@ def estimate_model(q_points, t_points, matches, keep=None, model="homography", n
         keep = np.ascontiguousarray(np.asarray(keep) != 0, dtype=np.uint8)
         if keep.shape != (len(q),):
             raise ValueError("keep must have one entry per query point")
+    return q, t, kind, rec, keep
+
+
+def _refine_rounds(n_rounds):
+    n_rounds = int(n_rounds)
+    if not 0 <= n_rounds <= _REFINE_MAX_ROUNDS:
+        raise ValueError("n_rounds must be in 0..8")
+    return n_rounds
+
+
+def _refine_points(q, t, kind, rec, keep, code, start, threshold, n_rounds, device):
+    """fdf_refine_points on _host_pair's arrays: (the refined (1,) record, the uint8 mask, the
+    accepted rounds)."""
+    out = np.zeros(1, dtype=MODEL_DTYPE)
+    mask = np.zeros(len(q), dtype=np.uint8)
+    rounds = ctypes.c_uint32()
+    rc = _native.load().fdf_refine_points(
+        context(device).handle, q.ctypes.data if len(q) else None,
+        t.ctypes.data if len(t) else None, len(q), len(t), rec.ctypes.data if len(q) else None,
+        keep.ctypes.data if keep is not None and len(q) else None, kind, code, start.ctypes.data,
+        threshold, n_rounds, out.ctypes.data, mask.ctypes.data if len(q) else None,
+        ctypes.addressof(rounds))
+    check(rc, "fdf_refine_points")
+    return out, mask, rounds.value
+
+
+def estimate_model(q_points, t_points, matches, keep=None, model="homography", n_hyp=256,
+                   threshold=3.0, seed=0, device=0, refine_rounds=0):
+    """RANSAC estimation of the affine map or homography that takes the query points to their
+    matches (fdf_ransac_points): (H as a (3, 3) float64 array or None when there is no model, the
+    (n_q,) bool inlier mask, the MODEL_DTYPE record).  ``q_points`` (n_q, 2) and ``t_points``
+    (n_t, 2) are both integer or both float32 arrays of (x, y); ``matches`` is match_descriptors'
+    result (or (n_q,) train indices, negative = none), ``keep`` an optional (n_q,) mask.
+    ``refine_rounds`` > 0 refits the model over its inliers that many times at most
+    (fdf_refine_points, the same threshold); 0 leaves the minimal sample's model."""
+    q, t, kind, rec, keep = _host_pair(q_points, t_points, matches, keep)
     code = _ransac_model(model)
     n_hyp, threshold, seed = _ransac_values(n_hyp, threshold, seed)
+    refine_rounds = _refine_rounds(refine_rounds)
     out = np.zeros(1, dtype=MODEL_DTYPE)
     mask = np.zeros(len(q), dtype=np.uint8)
     rc = _native.load().fdf_ransac_points(
@@ -1756,8 +1789,100 @@ def estimate_model(q_points, t_points, matches, keep=None, model="homography", n
         keep.ctypes.data if keep is not None and len(q) else None, kind, code, n_hyp, threshold,
         seed, out.ctypes.data, mask.ctypes.data if len(q) else None)
     check(rc, "fdf_ransac_points")
+    if refine_rounds:
+        out, mask, _ = _refine_points(q, t, kind, rec, keep, code, out, threshold, refine_rounds,
+                                      device)
     found = out["hypothesis"][0] != RANSAC_NONE
     return (out["h"][0].reshape(3, 3).copy() if found else None), mask.astype(bool), out[0]
+
+
+def refine_scratch_bytes(n_frames, q_cap):
+    """Bytes of refine_device's scratch tensor (fdf_refine_scratch_bytes)."""
+    n_frames, q_cap = int(n_frames), int(q_cap)
+    if not (0 <= n_frames <= 65535 and 0 <= q_cap <= _MATCH_MAX_CAP):
+        raise ValueError("at most 65535 frames and fewer than 2^32 - 1 queries")
+    v = ctypes.c_uint64()
+    check(_native.load().fdf_refine_scratch_bytes(n_frames, q_cap, ctypes.byref(v)),
+          "fdf_refine_scratch_bytes")
+    return v.value
+
+
+def refine_device(matches, q_offsets, q_coords, t_coords, t_offsets, models_in, models_out,
+                  scratch, keep=None, inliers=None, rounds=None, model="homography",
+                  threshold=3.0, n_rounds=2, stream=None, device=None):
+    """Least-squares refinement of ransac_device's models over their inliers, on the device
+    (fdf_refine_device).  The correspondences are ransac_device's (``matches``, ``q_offsets``,
+    ``q_coords``, ``t_coords``, ``t_offsets``, ``keep``); ``models_in`` (F, 11) float64 holds the
+    models to refine and ``models_out`` (which may be ``models_in``) gets the refined ones;
+    ``inliers`` (optional, (q_cap,) uint8) gets their inliers under ``threshold`` and ``rounds``
+    (optional, (F,) int32) the rounds each frame accepted, at most ``n_rounds`` (0..8).
+    ``scratch``: a uint8 tensor of refine_scratch_bytes(F, q_cap), 256-byte aligned, no
+    initialisation needed.  The result is a pure function of the inputs.  Asynchronous on
+    ``stream`` (default: torch's current stream)."""
+    import torch
+
+    _check_matches(matches, "matches", "q_cap")
+    q_cap = matches.shape[0]
+    n = _match_frames(torch, q_offsets, t_offsets)
+    kind = _check_coords(torch, q_coords, "q_coords", "q_cap", q_cap)
+    if _check_coords(torch, t_coords, "t_coords", "t_cap") != kind:
+        raise ValueError("q_coords and t_coords must have the same type")
+    t_cap = t_coords.shape[0]
+    for t, name in ((models_in, "models_in"), (models_out, "models_out")):
+        if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != 11 or t.shape[0] < n or \
+                not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous (F, 11) float64 tensor")
+    for t, name in ((keep, "keep"), (inliers, "inliers")):
+        if t is not None and (t.dtype != torch.uint8 or t.dim() != 1 or t.numel() < q_cap or
+                              not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous uint8 tensor with q_cap entries")
+    if rounds is not None and (rounds.dtype != torch.int32 or rounds.dim() != 1 or
+                               rounds.numel() < n or not rounds.is_contiguous()):
+        raise ValueError("rounds must be a contiguous int32 tensor with F entries")
+    code = _ransac_model(model)
+    _, threshold, _ = _ransac_values(1, threshold, 0)
+    n_rounds = _refine_rounds(n_rounds)
+    if scratch.dtype != torch.uint8 or scratch.dim() != 1 or not scratch.is_contiguous() or \
+            scratch.numel() < refine_scratch_bytes(n, q_cap):
+        raise ValueError("scratch must be a uint8 tensor of refine_scratch_bytes(F, q_cap)")
+    if scratch.data_ptr() % 256:
+        raise ValueError("scratch must be 256-byte aligned")
+    _check_one_device("refine_device",
+                      [matches, q_offsets, q_coords, t_coords, t_offsets, models_in, models_out,
+                       scratch] + [t for t in (keep, inliers, rounds) if t is not None])
+    dev, stream = _device_stream(torch, matches, device, stream)
+    rc = _native.load().fdf_refine_device(
+        context(dev).handle, n, matches.data_ptr(), keep.data_ptr() if keep is not None else None,
+        q_cap, q_offsets.data_ptr(), q_coords.data_ptr(), t_coords.data_ptr(), t_cap,
+        t_offsets.data_ptr(), kind, code, models_in.data_ptr(), threshold, n_rounds,
+        models_out.data_ptr(), inliers.data_ptr() if inliers is not None else None,
+        rounds.data_ptr() if rounds is not None else None, scratch.data_ptr(), scratch.numel(),
+        ctypes.c_void_p(stream.cuda_stream))
+    check(rc, "fdf_refine_device")
+
+
+def refine_model(q_points, t_points, matches, estimate, keep=None, model="homography",
+                 threshold=3.0, n_rounds=2, device=0):
+    """Least-squares refinement of one model over its inliers (fdf_refine_points): (H as a (3, 3)
+    float64 array or None when ``estimate`` holds no model, the (n_q,) bool inlier mask, the
+    MODEL_DTYPE record, the rounds accepted).  The point sets, ``matches`` and ``keep`` are
+    estimate_model's; ``estimate`` is its record, or a (3, 3) array to start from."""
+    q, t, kind, rec, keep = _host_pair(q_points, t_points, matches, keep)
+    code = _ransac_model(model)
+    _, threshold, _ = _ransac_values(1, threshold, 0)
+    n_rounds = _refine_rounds(n_rounds)
+    start = np.zeros(1, dtype=MODEL_DTYPE)
+    given = np.asarray(estimate)
+    if given.dtype == MODEL_DTYPE and given.size == 1:
+        start[0] = given.reshape(-1)[0]
+    elif given.dtype.kind in "fiu" and given.size == 9:
+        start["h"][0] = given.astype(np.float64).reshape(-1)
+    else:
+        raise TypeError("estimate must be a MODEL_DTYPE record or a (3, 3) array")
+    out, mask, rounds = _refine_points(q, t, kind, rec, keep, code, start, threshold, n_rounds,
+                                       device)
+    found = out["hypothesis"][0] != RANSAC_NONE
+    return (out["h"][0].reshape(3, 3).copy() if found else None), mask.astype(bool), out[0], rounds
 
 
 __all__ = ["NORTH", "EAST", "SOUTH", "WEST", "circle", "calculate_offsets", "context",
@@ -1776,6 +1901,7 @@ __all__ = ["NORTH", "EAST", "SOUTH", "WEST", "circle", "calculate_offsets", "con
            "match_filter_device", "unpack_matches", "match_descriptors",
            "MODEL_DTYPE", "RANSAC_NONE", "ransac_sample", "ransac_scratch_bytes", "ransac_device",
            "unpack_models", "estimate_model",
+           "refine_scratch_bytes", "refine_device", "refine_model",
            "detect_rgb_array", "detector_rgb", "rgb_to_luma", "detect_device_rgb",
            "score_rings", "score_rings_device", "keypoint_score_max_threshold",
            "keypoint_score_sum_abs_difference", "NonMaximalSuppression"]

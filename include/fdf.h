@@ -38,7 +38,8 @@ extern "C" {
  * fdf_match_device, fdf_match_filter_device and fdf_match_points, and fdf_resize_taps,
  * fdf_resize_device, fdf_resize_frame, fdf_pyramid_plan, fdf_pyramid_taps and
  * fdf_pyramid_device, and fdf_harris_codes, fdf_harris_device and fdf_harris_points, and
- * fdf_ransac_sample, fdf_ransac_scratch_bytes, fdf_ransac_device and fdf_ransac_points. */
+ * fdf_ransac_sample, fdf_ransac_scratch_bytes, fdf_ransac_device and fdf_ransac_points, and
+ * fdf_refine_scratch_bytes, fdf_refine_device and fdf_refine_points. */
 #define FDF_ABI_VERSION 6
 
 /* Status codes.  Shapes the reference maps to an empty Vec return FDF_OK with 0 points. */
@@ -771,6 +772,109 @@ int fdf_ransac_points(fdf_ctx* ctx, const void* q_coords, const void* t_coords, 
                       size_t n_t, const fdf_match* matches, const uint8_t* keep, uint32_t coords,
                       uint32_t model, uint32_t n_hyp, float threshold, uint32_t seed,
                       fdf_model* model_out, uint8_t* inliers_out);
+
+/*
+ * Least-squares refinement of the models over their inliers (extension: the step after
+ * fdf_ransac_device, the refit that estimateAffine2D / findHomography apply to their winner).
+ * Like the estimation it is a pure function of its inputs: every floating-point step below is
+ * one IEEE binary64 operation rounded once, only + - * / and the absolute value are used, and
+ * every sum has one fixed order.
+ *
+ * Inputs.  The correspondences of frame f, numbered j = 0..M-1, are the RANSAC block's, from the
+ * same arrays (matches, keep, capacities, offsets, coordinates, `coords`).  d_models_in[f] is the
+ * frame's model, `model` says which kind (s and N as above), `threshold` need not be the one the
+ * model was estimated with, n_rounds is 0..8.
+ *
+ * Per frame.  hypothesis == FDF_RANSAC_NONE: the record is copied unchanged, every inlier byte of
+ * the frame is 0 and rounds is 0.  Otherwise the current model is d_models_in[f].h, the current
+ * set is the correspondences that the Score rule above makes inliers of it under `threshold`
+ * (computed, not read from any bytes) and the current count n is the set's size.  Then n_rounds
+ * times:
+ *
+ *  1. Normalise.  Over the current set: cx = Sx / n and cy = Sy / n with Sx, Sy the sums of x and
+ *     of y and n as a double; d = the sum of (|x - cx| + |y - cy|); s = (n + n) / d.  The same
+ *     for (u, v) gives cu, cv, e and t = (n + n) / e.  The round fails if n is below the model's
+ *     sample size or unless 0 < d < infinity and 0 < e < infinity.  X = (x - cx) * s, Y = (y - cy) * s,
+ *     U = (u - cu) * t, V = (v - cv) * t.
+ *  2. Normal equations.  A member gives the Fit rule's two rows in normalised coordinates,
+ *       r0 = [X, Y, 1, 0, 0, 0, -(U X), -(U Y)],  r1 = [0, 0, 0, X, Y, 1, -(V X), -(V Y)]
+ *     (affine: the first six columns).  For i <= j < N, G[i][j] = the sum of
+ *     r0[i] * r0[j] + r1[i] * r1[j] and G[j][i] = G[i][j]; g[i] = the sum of
+ *     r0[i] * U + r1[i] * V.  A product with a factor that is one of the zeros written above is
+ *     not formed and not added (so G[0][0] sums X * X alone, G[0][3] is 0 and g[0] sums X * U); a
+ *     factor 1 is exact.  The sign of a zero is free here as everywhere.
+ *  3. Order.  Every sum of 1 and 2 is formed like this: correspondence j belongs to lane
+ *     j mod 256; a lane starts from +0.0 and adds the terms of its members in increasing j
+ *     (sum = sum + term); then the 256 lane sums fold as sum[t] = sum[t] + sum[t + step] for
+ *     every t < step, with step = 128, 64, .., 1, and sum[0] is the result.  n is the same sum
+ *     of ones (exact).
+ *  4. Solve G hn = g by the Fit rule's elimination and back substitution, unchanged: the lowest
+ *     row among the largest magnitudes, a NaN never wins, a pivot below 2^-20 fails the round.
+ *     hn8 = 1; affine: hn6 = hn7 = 0.
+ *  5. Denormalise, H = T2^-1 Hn T1 with T1 = [s 0 -s cx; 0 s -s cy; 0 0 1] and
+ *     T2^-1 = [1/t 0 cu; 0 1/t cv; 0 0 1], as this sequence: for each row r = 0, 1, 2 of Hn
+ *       a0 = hn[3r] * s,  a1 = hn[3r+1] * s,  a2 = (hn[3r+2] - a0 * cx) - a1 * cy;
+ *     with A the three rows (a0, a1, a2), for each column c
+ *       H[c] = A[0][c] / t + cu * A[2][c],  H[3+c] = A[1][c] / t + cv * A[2][c],  H[6+c] = A[2][c];
+ *     h_k = H[k] / H[8] for k < 8 and h8 = 1.  The round fails unless 2^-20 <= |H[8]| < infinity.
+ *     Affine: A's last row is 0 0 1, so h0 = A[0][0] / t, h1 = A[0][1] / t, h2 = A[0][2] / t + cu,
+ *     h3 = A[1][0] / t, h4 = A[1][1] / t, h5 = A[1][2] / t + cv, h6 = h7 = 0, h8 = 1, without the
+ *     products by zero and without a division by H[8].  Either kind: the round fails if any h_k
+ *     is not finite.
+ *  6. Re-score all M correspondences under h.  The round is accepted iff it did not fail and the
+ *     new count is at least the current one; then h, its set and its count become current.
+ *     Otherwise the frame stops and keeps what was current.
+ *
+ * Output.  d_models_out[f] (d_models_out may be d_models_in) gets the current h, n_corr = M,
+ * n_inliers = the current count, and hypothesis and n_valid as they came.  d_inliers (optional,
+ * q_cap bytes) follows the RANSAC rule: for every i in [qo[0], min(qo[n_frames], q_cap)) and for
+ * no other byte, 1 if i is a correspondence in its frame's current set and 0 otherwise.  d_rounds
+ * (optional, n_frames uint32_t) gets the number of accepted rounds.  n_rounds == 0 recounts and
+ * rewrites the bytes under `threshold` and leaves h as it came.
+ *
+ * Example.  The RANSAC example's six pairs and its model 1 0 3 0 1 5 0 0 1, T = 1, one round.
+ * The set is pairs 0 1 2 3 5: n = 5, cx = 8, cy = 4.6, d = 53.6, s = 10 / 53.6 =
+ * 0.18656716417910446; cu = 11, cv = 9.6, e = 53.6, t = s.  Both kinds of model accept the round
+ * (rounds 1) with 5 inliers and the bytes 1 1 1 1 0 1.  Affine: h = 1 0 3 0 1 5 0 0 1 again,
+ * exactly.  Homography, the rounding of eight unknowns over five exact pairs:
+ *   h0 = 0x1.0000000000001p+0    h1 = -0x1.dc507e631a7ddp-54   h2 = 0x1.7fffffffffffdp+1
+ *   h3 = 0x1.886f0037424e0p-54   h4 = 0x1.0000000000000p+0     h5 = 0x1.3ffffffffffffp+2
+ *   h6 = 0x1.302010db87537p-57   h7 = -0x1.a85e37930f5e6p-57   h8 = 1
+ *
+ * fdf_refine_scratch_bytes: host only; the size of fdf_refine_device's d_scratch (256-byte
+ * aligned; needs no initialisation and may be reused in stream order): 32 bytes per query index
+ * and 4 per frame.  FDF_ERR_ARG: NULL bytes, n_frames > 65535, q_cap of 2^32 - 1 or more.
+ *
+ * fdf_refine_device: two kernels, asynchronous on `stream` (NULL = the HIP null stream); it takes
+ * no context lock and uses no context workspace, it only binds the context's device; nothing is
+ * allocated and nothing returns to the host.  FDF_ERR_ARG, synchronously and with nothing
+ * launched: n_frames > 65535, a cap of 2^32 - 1 or more, a coords or model value that is none of
+ * the above, a threshold that is negative or not finite, n_rounds > 8; and, unless n_frames == 0
+ * (FDF_OK, nothing written): a NULL required pointer (all but d_keep, d_inliers and d_rounds),
+ * matches, coordinates or models that are not 8-byte aligned, rounds that are not 4-byte aligned,
+ * a scratch that is not 256-byte aligned or too small.  The bounds guarantee of
+ * fdf_ransac_device holds: whatever the inputs hold, the models included, no access leaves the
+ * buffers.
+ *
+ * fdf_refine_points: one pair of host sets as fdf_ransac_points takes them and the model to
+ * refine, synchronous; inliers_out (n_q bytes) and rounds_out may be NULL, model_out may be
+ * model_in.  Copies through device buffers allocated and freed by the call and runs the same
+ * kernels; the context's workspace and retained result are untouched, so fdf_fetch_last stays
+ * valid.
+ */
+int fdf_refine_scratch_bytes(uint32_t n_frames, uint64_t q_cap, uint64_t* bytes);
+int fdf_refine_device(fdf_ctx* ctx, uint32_t n_frames, const fdf_match* d_matches,
+                      const uint8_t* d_keep, uint64_t q_cap, const uint64_t* d_q_offsets,
+                      const void* d_q_coords, const void* d_t_coords, uint64_t t_cap,
+                      const uint64_t* d_t_offsets, uint32_t coords, uint32_t model,
+                      const fdf_model* d_models_in, float threshold, uint32_t n_rounds,
+                      fdf_model* d_models_out, uint8_t* d_inliers, uint32_t* d_rounds,
+                      void* d_scratch, uint64_t scratch_bytes, void* stream);
+int fdf_refine_points(fdf_ctx* ctx, const void* q_coords, const void* t_coords, size_t n_q,
+                      size_t n_t, const fdf_match* matches, const uint8_t* keep, uint32_t coords,
+                      uint32_t model, const fdf_model* model_in, float threshold,
+                      uint32_t n_rounds, fdf_model* model_out, uint8_t* inliers_out,
+                      uint32_t* rounds_out);
 
 /*
  * Exact bilinear resize and the scale pyramid (extension: the reference detects at one scale;

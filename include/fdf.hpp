@@ -20,6 +20,7 @@
 //   (none: ... and describe)         --                   fdf::keypoint_descriptors(img, points, ...)
 //   (none: ... and match)            --                   fdf::match_descriptors(q_desc, t_desc, ...)
 //   (none: ... and fit a model)      --                   fdf::estimate_model(q_points, t_points, matches, ...)
+//   (none: ... and refine it)        --                   fdf::refine_model(q_points, t_points, matches, estimate, ...)
 //   (none: ... over a scale pyramid) --                   fdf::resize, fdf::pyramid_plan, fdf::build_pyramid
 //
 // Where the reference panics (n < 9, n > 16, degenerate sizes) these throw fdf::Error.
@@ -367,6 +368,43 @@ inline ModelEstimate estimate_model(const std::vector<Point>& q_points,
                                     float threshold = 3.0f, uint32_t seed = 0) {
     return estimate_model(q_points, t_points, matches, keep, model, n_hyp, threshold, seed,
                           thread_context());
+}
+
+// Least-squares refinement of estimate_model's result over its inliers (extension,
+// fdf_refine_points; include/fdf.h has the normalisation, the order of the sums and the
+// acceptance rule).  The point sets, `matches` and `keep` are estimate_model's; at most
+// `n_rounds` (0..8) rounds, each kept only if it loses no inlier under `threshold`.
+struct RefinedModel {
+    fdf_model model;                  // hypothesis and n_valid as they came
+    std::vector<uint8_t> inliers;     // 1 for the queries that are inliers of the refined model
+    uint32_t rounds = 0;              // rounds accepted
+    bool found() const { return model.hypothesis != FDF_RANSAC_NONE; }
+};
+inline RefinedModel refine_model(const std::vector<Point>& q_points,
+                                 const std::vector<Point>& t_points,
+                                 const std::vector<Match>& matches,
+                                 const std::vector<uint8_t>* keep, uint32_t model,
+                                 const fdf_model& estimate, float threshold, uint32_t n_rounds,
+                                 Context& ctx) {
+    if (matches.size() != q_points.size() || (keep && keep->size() != q_points.size()))
+        throw Error(FDF_ERR_ARG, "refine_model: one match and keep flag per query point");
+    RefinedModel out;
+    out.inliers.resize(q_points.size());
+    check(fdf_refine_points(ctx.get(), q_points.data(), t_points.data(), q_points.size(),
+                            t_points.size(), matches.data(), keep ? keep->data() : nullptr,
+                            FDF_COORDS_U32, model, &estimate, threshold, n_rounds, &out.model,
+                            out.inliers.data(), &out.rounds),
+          "fdf_refine_points");
+    return out;
+}
+inline RefinedModel refine_model(const std::vector<Point>& q_points,
+                                 const std::vector<Point>& t_points,
+                                 const std::vector<Match>& matches, const fdf_model& estimate,
+                                 const std::vector<uint8_t>* keep = nullptr,
+                                 uint32_t model = FDF_MODEL_HOMOGRAPHY, float threshold = 3.0f,
+                                 uint32_t n_rounds = 2) {
+    return refine_model(q_points, t_points, matches, keep, model, estimate, threshold, n_rounds,
+                        thread_context());
 }
 
 // Exact bilinear resize and the scale pyramid (extension, fdf_resize_frame and
