@@ -61,13 +61,17 @@ constexpr int kSweepWavesPerEU = 4;
 // neighbouring bands' rows, so the band also tests one row each side (scores only).
 __host__ __device__ inline uint32_t band_halo(uint32_t nms) { return nms ? 1u : 0u; }
 
-// LDS of one workgroup: the keypoint bitmap of the band's R rows plus the NMS halo rows (NMS
-// then clears the suppressed keypoints in place; one pad word after the bitmap lets bit
-// look-ups read two words unconditionally), 4 candidate FIFOs (+ batch staging), and for NMS
-// the band's keypoint scores: a list of kScoreListCap (position, score) entries and per-row /
-// per-4-word-block keypoint counts that turn a bitmap position into its raster rank.  The
-// FIFOs, staging and score list are contiguous: once the sweep is done they hold the scores
-// in rank order (`nms_area`, u16 entries; the FIFO part alone for band_nms_lds).
+// LDS of one workgroup: the keypoint bitmap of the band's R rows plus the NMS halo rows (the
+// spill and dense NMS tiers then clear the suppressed keypoints in place; one pad word after
+// the bitmap lets bit look-ups read two words unconditionally), 4 candidate FIFOs (+ batch
+// staging), and for NMS the band's keypoint scores: a list of kScoreListCap (position, score)
+// entries and per-row / per-4-word-block keypoint counts that turn a bitmap position into its
+// raster rank.  The FIFOs, staging and score list are contiguous: once the sweep is done they
+// hold the scores in rank order (`nms_area`, u16 entries).  band_nms_lds (at most
+// kScoreListCap keypoints) ranks into the FIFO part alone and keeps, at `stage`, one kill bit
+// per rank: 64 kill words in wave 0's staging area (stage + 0 .. 255) and their 64 exclusive
+// popcount prefixes in wave 1's (stage + 256 .. 511); the band's points are then written from
+// the list, each at its rank less the kills below it.
 constexpr uint32_t kScoreListCap = 2048;
 constexpr uint32_t kRankBlock = 4;            // bitmap words per rank-prefix block
 // band_nms_lds ranks the list's scores as u16 into the 4 candidate FIFOs

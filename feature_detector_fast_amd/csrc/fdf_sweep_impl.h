@@ -1,8 +1,7 @@
 // fdf_sweep_impl.h -- column-sweep FAST-9..16 kernel for MI355X (gfx950), the production path.
 // Included by fdf_sweep.hip (grey frames: FDF_SWEEP_RGB 0, namespace fdfk::grey),
-// fdf_sweep_latency.hip (grey frames, units leave their last 8-step block early and the emit
-// keeps nothing in registers, FDF_SWEEP_TU_EXIT 1 and FDF_SWEEP_TU_EMIT_REGS 0: namespace
-// fdfk::grey_lat) and fdf_sweep_rgb.hip (RGB8 frames converted to luma in the row and window
+// fdf_sweep_latency.hip (grey frames, units leave their last 8-step block early,
+// FDF_SWEEP_TU_EXIT 1: namespace fdfk::grey_lat) and fdf_sweep_rgb.hip (RGB8 frames converted to luma in the row and window
 // loads: FDF_SWEEP_RGB 1, namespace fdfk::rgb); each translation unit instantiates its 24
 // kernels.
 //
@@ -33,8 +32,9 @@
 // NMS (src/fast_simd.rs:589-616) runs once the whole band is tested: the band also tests one
 // row above and below it, so every neighbour of its keypoints is in the bitmap, and each
 // keypoint is compared with the scores of the neighbours the bitmap marks.  The band's
-// keep-bits are then written to its output slot (its points in raster order, or the bitmap
-// if they do not fit) and compact_kernel orders all slots.
+// kept keypoints are then written to its output slot (its points in raster order -- from the
+// ranked score list where the band's keypoints fit it, from the bitmap's keep-bits otherwise
+// -- or the bitmap if they do not fit) and compact_kernel orders all slots.
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -58,7 +58,7 @@ constexpr bool kRgb = FDF_SWEEP_RGB != 0;
 // frames read in place over PCIe was measured slower (PCIe read throughput,
 // not latency, bounds that kernel).
 //
-// The two per-unit parameters of this header:
+// The per-unit parameter of this header:
 // FDF_SWEEP_TU_EXIT (default 0): units that end inside an 8-step block leave it at their last
 // row (the latency instances of fdf_sweep_latency.hip: a single frame's 3-row units skip 4
 // padding steps).  The exit tests perturb the long-unit loop's code (512 x 1080p max-t
@@ -67,13 +67,6 @@ constexpr bool kRgb = FDF_SWEEP_RGB != 0;
 #define FDF_SWEEP_TU_EXIT 0
 #endif
 constexpr bool kExitInBlock = FDF_SWEEP_TU_EXIT != 0;
-// FDF_SWEEP_TU_EMIT_REGS (default 1): the max-t emit's write pass reuses the count pass's
-// bitmap groups from registers (sweep_band).  The latency unit sets it to 0:
-// its max-t kernels spill with it.
-#ifndef FDF_SWEEP_TU_EMIT_REGS
-#define FDF_SWEEP_TU_EMIT_REGS 1
-#endif
-constexpr bool kEmitRegs = FDF_SWEEP_TU_EMIT_REGS != 0;
 constexpr int kPx = kRgb ? 3 : 1;
 
 // A lane's kLaneCols = 16 bytes of one pixel row are one u32x4.
@@ -886,11 +879,8 @@ __device__ uint32_t band_rank_prefixes(const uint32_t* bitmap, uint32_t R2, uint
 // Strict 3x3 maximum of list entry e (src/fast_simd.rs:596-615) against the scores of its
 // neighbouring keypoints, read by raster rank from `sranked`; rows 3 / h-4 and the rows
 // outside the band are reported as suppressed / not compared by the caller's rules below.
-// Returns e with its score field replaced by 1 (suppressed) or 0 (kept).
-// RANKED (the LDS list, at most kScoreListCap entries): the scatter left the entry's raster
-// rank + 1 in its low 12 bits (its score is at that rank), so its own rank is not looked up
-// again.
-template <bool RANKED>
+// Returns e with its score field replaced by 1 (suppressed) or 0 (kept).  (The spill tier;
+// the LDS-list tier decides the same way in nms_entry_kill.)
 __device__ __forceinline__ uint32_t nms_entry(uint32_t e, const uint32_t* bitmap, uint32_t nw,
                                               uint32_t nb_blocks, uint32_t y0, PosCode W,
                                               uint32_t H, uint32_t R2, const uint16_t* sranked,
@@ -902,12 +892,11 @@ __device__ __forceinline__ uint32_t nms_entry(uint32_t e, const uint32_t* bitmap
     const uint32_t low = e & 0xfffu;
     bool suppressed = y == 3 || y == H - 4;
     if (low != 0 && !suppressed) {
-        const uint32_t own = RANKED ? (uint32_t)sranked[low - 1u] : low;
+        const uint32_t own = low;
         uint32_t mx = 0;
         const uint32_t mid = bits3(bitmap + row * nw, (int)x);
         if (mid & 5u) {
-            const uint32_t ro = RANKED ? low - 1u
-                                       : bitmap_rank(bitmap, bprefix, rprefix, nw, nb_blocks, row, x);
+            const uint32_t ro = bitmap_rank(bitmap, bprefix, rprefix, nw, nb_blocks, row, x);
             if (mid & 1u) mx = max(mx, (uint32_t)sranked[ro - 1]);
             if (mid & 4u) mx = max(mx, (uint32_t)sranked[ro + 1]);
         }
@@ -930,9 +919,9 @@ __device__ __forceinline__ uint32_t nms_entry(uint32_t e, const uint32_t* bitmap
     return (e & ~0xfffu) | (suppressed ? 1u : 0u);
 }
 
-// Rank-order scatter of list entry e: a keypoint with a neighbouring keypoint puts its score
-// at its raster rank; an isolated one is kept without comparison, marked by a zero score.
-template <bool RANKED = false>
+// Rank-order scatter of list entry e (the spill tier): a keypoint with a neighbouring keypoint
+// puts its score at its raster rank; an isolated one is kept without comparison, marked by a
+// zero score.
 __device__ __forceinline__ uint32_t nms_scatter(uint32_t e, const uint32_t* bitmap, uint32_t nw,
                                                 uint32_t R2, uint32_t nb_blocks, PosCode W,
                                                 uint16_t* sranked, const uint16_t* bprefix,
@@ -942,8 +931,68 @@ __device__ __forceinline__ uint32_t nms_scatter(uint32_t e, const uint32_t* bitm
     if (neighbour_bits(bitmap, nw, R2, row, x) == 0) return e & ~0xfffu;
     const uint32_t rank = bitmap_rank(bitmap, bprefix, rprefix, nw, nb_blocks, row, x);
     sranked[rank] = (uint16_t)(e & 0xfffu);
-    if constexpr (RANKED) return (e & ~0xfffu) | (rank + 1u);
     return e;
+}
+
+// The LDS-list tier keeps no suppressed flag in the entry and clears no bitmap bit: every
+// entry is ranked (rank + 1 in its low 12 bits, its score at sranked[rank]) and a keypoint
+// that is not output sets bit `rank` of the band's kKillWords kill words.  The words and
+// their exclusive popcount prefixes live in the staging areas of waves 0 and 1 (SweepLayout::
+// stage), which are free once the sweep is over.
+constexpr uint32_t kKillWords = kScoreListCap / 32;
+static_assert(kKillWords == 64, "one wave scans the kill words; words and prefixes fill two staging areas");
+
+// Rank-order scatter of list entry e of the LDS-list tier: every keypoint, isolated or not,
+// puts its score at its raster rank and keeps rank + 1 in place of the score.
+__device__ __forceinline__ uint32_t nms_scatter_ranked(uint32_t e, const uint32_t* bitmap,
+                                                       uint32_t nw, uint32_t nb_blocks, PosCode W,
+                                                       uint16_t* sranked, const uint16_t* bprefix,
+                                                       const uint32_t* rprefix) {
+    uint32_t row, x;
+    pos_decode(W, e >> 12, row, x);
+    const uint32_t rank = bitmap_rank(bitmap, bprefix, rprefix, nw, nb_blocks, row, x);
+    sranked[rank] = (uint16_t)(e & 0xfffu);
+    return (e & ~0xfffu) | (rank + 1u);
+}
+
+// Suppression of ranked list entry e, decided as nms_entry decides it (strict maximum against
+// the score of every neighbour the pre-NMS bitmap marks; rows 3 / h-4 always suppressed): a
+// suppressed keypoint sets its kill bit, and so does every keypoint of bitmap rows 0 and
+// R2 - 1 (neighbours only, never output).  Scores are >= 1, so a keypoint without
+// neighbours (mx = 0) is kept.
+__device__ __forceinline__ void nms_entry_kill(uint32_t e, const uint32_t* bitmap, uint32_t nw,
+                                               uint32_t nb_blocks, uint32_t y0, PosCode W,
+                                               uint32_t H, uint32_t R2, const uint16_t* sranked,
+                                               uint32_t* kill, const uint16_t* bprefix,
+                                               const uint32_t* rprefix) {
+    uint32_t row, x;
+    pos_decode(W, e >> 12, row, x);
+    const uint32_t rank = (e & 0xfffu) - 1u;
+    const uint32_t y = y0 - 1 + row;
+    bool suppressed = row == 0 || row == R2 - 1 || y == 3 || y == H - 4;
+    if (!suppressed) {
+        const uint32_t own = sranked[rank];
+        uint32_t mx = 0;
+        const uint32_t mid = bits3(bitmap + row * nw, (int)x);
+        if (mid & 1u) mx = max(mx, (uint32_t)sranked[rank - 1]);
+        if (mid & 4u) mx = max(mx, (uint32_t)sranked[rank + 1]);
+#pragma unroll
+        for (int d = -1; d <= 1; d += 2) {
+            const uint32_t nbits = bits3(bitmap + (row + d) * nw, (int)x);
+            if (nbits) {
+                uint32_t r = bitmap_rank(bitmap, bprefix, rprefix, nw, nb_blocks, row + d, x - 1);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    if ((nbits >> k) & 1u) {
+                        mx = max(mx, (uint32_t)sranked[r]);
+                        ++r;
+                    }
+                }
+            }
+        }
+        suppressed = own <= mx;
+    }
+    if (suppressed) atomicOr(&kill[rank >> 5], 1u << (rank & 31u));
 }
 
 __device__ __forceinline__ void nms_clear(uint32_t e, uint32_t* bitmap, uint32_t nw, PosCode W) {
@@ -960,28 +1009,42 @@ __device__ __forceinline__ void nms_clear(uint32_t e, uint32_t* bitmap, uint32_t
 // rank order, then each keypoint of the band's own rows reads its neighbours' scores by
 // rank, and the suppressed ones are cleared once every comparison has read the bitmap.
 // Rows 3 and h-4 are never output (:590-592, :342).
-//   n <= cap: the list is in LDS and the ranked scores go to the FIFO area.
+//   n <= cap (band_nms_lds): the list is in LDS and the ranked scores go to the FIFO area.
+//   The bitmap is not touched: the keypoints that are not output are recorded by rank in the
+//   kill words (`kill`: kKillWords words, then their kKillWords exclusive popcount prefixes),
+//   and sweep_band writes the band's points from the list (or clears the killed bits itself
+//   where it needs the bitmap).  Returns the band's output count, n less the kills, or
+//   kNoListEmit when the kill words were not made (ablation runs).
 //   n > cap (the band_nms_spill variant): entries past the LDS list were appended to the
 //   band's slot (`spill`); the LDS entries move to registers (kSpillPer per thread), so the
 //   ranked scores can use the whole FIFO + staging + list area.
+constexpr uint32_t kNoListEmit = ~0u;
+
 template <int NMS, int N>
-__device__ void band_nms_lds(uint32_t* bitmap, uint32_t rows, uint32_t nw, uint32_t y0, PosCode W,
-                             uint32_t H, uint32_t* slist, uint32_t n, uint16_t* sranked,
-                             uint16_t* bprefix, uint32_t* rprefix, uint32_t* total, uint32_t flags) {
+__device__ uint32_t band_nms_lds(const uint32_t* bitmap, uint32_t rows, uint32_t nw, uint32_t y0,
+                                 PosCode W, uint32_t H, uint32_t* slist, uint32_t n,
+                                 uint16_t* sranked, uint32_t* kill, uint16_t* bprefix,
+                                 uint32_t* rprefix, uint32_t* total, uint32_t flags) {
     const uint32_t tid = threadIdx.x;
     const uint32_t R2 = rows + 2, nb_blocks = (nw + kRankBlock - 1) / kRankBlock;
     band_rank_prefixes(bitmap, R2, nw, bprefix, rprefix, total);
-    if (flags & kFlagNmsPrefixOnly) return;
+    if (flags & kFlagNmsPrefixOnly) return kNoListEmit;
+    if (tid < kKillWords) kill[tid] = 0u;
     for (uint32_t i = tid; i < n; i += kThreads)
-        slist[i] = nms_scatter<true>(slist[i], bitmap, nw, R2, nb_blocks, W, sranked, bprefix,
-                                     rprefix);
+        slist[i] = nms_scatter_ranked(slist[i], bitmap, nw, nb_blocks, W, sranked, bprefix, rprefix);
     __syncthreads();
     for (uint32_t i = tid; i < n; i += kThreads)
-        slist[i] = nms_entry<true>(slist[i], bitmap, nw, nb_blocks, y0, W, H, R2, sranked, bprefix,
-                                   rprefix);
+        nms_entry_kill(slist[i], bitmap, nw, nb_blocks, y0, W, H, R2, sranked, kill, bprefix,
+                       rprefix);
     __syncthreads();
-    for (uint32_t i = tid; i < n; i += kThreads) nms_clear(slist[i], bitmap, nw, W);
+    if (tid < kKillWords) {   // wave 0: exclusive popcount prefix of the kill words
+        const uint32_t c = (uint32_t)__popc(kill[tid]);
+        const uint32_t inc = wave_incl_scan(c);
+        kill[kKillWords + tid] = inc - c;
+        if (tid == kKillWords - 1) *total = n - inc;
+    }
     __syncthreads();
+    return *total;
 }
 
 constexpr uint32_t kSpillPer = kScoreListCap / kThreads;
@@ -1005,10 +1068,10 @@ __device__ void band_nms_spill(uint32_t* bitmap, uint32_t rows, uint32_t nw, uin
     __syncthreads();
 #pragma unroll
     for (uint32_t j = 0; j < kSpillPer; ++j)
-        ent[j] = nms_entry<false>(ent[j], bitmap, nw, nb_blocks, y0, W, H, R2, sranked, bprefix,
+        ent[j] = nms_entry(ent[j], bitmap, nw, nb_blocks, y0, W, H, R2, sranked, bprefix,
                                   rprefix);
     for (uint32_t i = tid; i < n - cap; i += kThreads)
-        spill[i] = nms_entry<false>(spill[i], bitmap, nw, nb_blocks, y0, W, H, R2, sranked, bprefix,
+        spill[i] = nms_entry(spill[i], bitmap, nw, nb_blocks, y0, W, H, R2, sranked, bprefix,
                                     rprefix);
     __syncthreads();
 #pragma unroll
@@ -1318,16 +1381,21 @@ __device__ __forceinline__ uint32_t sweep_band(const BandParams& P, uint8_t* sme
 
     const uint32_t nwords = rows * nw;
     const RowDiv nwd = make_rowdiv(nw);
+    // the LDS-list tier's kill words and their prefixes (band_nms_lds), list entries and count
+    uint32_t* kill = reinterpret_cast<uint32_t*>(smem_raw + L.stage);
+    static_assert(2 * kKillWords * 4 <= 4 * 64 * 4, "kill words and prefixes fit the staging areas");
+    uint32_t list_n = 0, list_total = kNoListEmit;
     if constexpr (NMS != kNmsOff) {
         const uint32_t n = *sh.slist_n;
         if (tid == 0 && P.kp_stats) atomicAdd(P.kp_stats, n);
         if (ablation_flags(P.flags) & kFlagNoNms) {
         } else if (n <= sh.slist_cap) {
-            band_nms_lds<NMS, N>(bitmap, rows, nw, y0, sh.pc, H, sh.slist, n,
-                                 reinterpret_cast<uint16_t*>(smem_raw + L.pq),
-                                 reinterpret_cast<uint16_t*>(smem_raw + L.bprefix),
-                                 reinterpret_cast<uint32_t*>(smem_raw + L.rprefix), unit_ctr + 2,
-                                 ablation_flags(P.flags));
+            list_n = n;
+            list_total = band_nms_lds<NMS, N>(bitmap, rows, nw, y0, sh.pc, H, sh.slist, n,
+                                              reinterpret_cast<uint16_t*>(smem_raw + L.pq), kill,
+                                              reinterpret_cast<uint16_t*>(smem_raw + L.bprefix),
+                                              reinterpret_cast<uint32_t*>(smem_raw + L.rprefix),
+                                              unit_ctr + 2, ablation_flags(P.flags));
         } else if (n - sh.slist_cap <= sh.spill_cap && n <= L.nms_area_entries) {
             // more keypoints than the LDS list holds: the rest were appended to the slot
             band_nms_spill<NMS, N>(bitmap, rows, nw, y0, sh.pc, H, sh.slist, sh.slist_cap, sh.spill, n,
@@ -1345,56 +1413,46 @@ __device__ __forceinline__ uint32_t sweep_band(const BandParams& P, uint8_t* sme
             }
             __syncthreads();
         }
-        // the band's own rows are now its keep-bits
+        // the band's own rows are now its keep-bits (the list tier: once its kills are cleared)
     }
     const uint32_t* keep = bitmap + halo * nw;
     if constexpr (kDebugBuild) ph[2] = __builtin_amdgcn_s_memtime();   // NMS done
+    uint8_t* slot = P.slots + (uint64_t)task * P.slot_bytes;
 
-    // ---- count keep-bits and write the band slot
-    // Each wave owns a contiguous quarter of the bitmap and sweeps it 256 words per round:
-    // lane = 4 words of one row (rows are whole 4-word groups, bitmap_words_per_row), one
-    // 16-byte LDS read each, and a wave prefix sum of the lanes' keypoint counts places the
-    // round's points consecutively in the slot.
+    // ---- count the band's points and write the band slot
+    // The LDS-list tier (from_list, workgroup-uniform) has its count from the kill words and
+    // writes its points from the ranked list: a kept entry's output index is its raster rank
+    // less the kills below it, so the points land in raster order whatever order the list is
+    // in, and the bitmap is not read again.
+    // The other tiers and NMS off count and write the bitmap's keep-bits: each wave owns a
+    // contiguous quarter of the bitmap and sweeps it 256 words per round: lane = 4 words of
+    // one row (rows are whole 4-word groups, bitmap_words_per_row), one 16-byte LDS read
+    // each, and a wave prefix sum of the lanes' keypoint counts places the round's points
+    // consecutively in the slot.
+    const bool from_list = list_total != kNoListEmit;
     const uint4* keep4 = reinterpret_cast<const uint4*>(keep);
     const uint32_t ngroups = nwords / 4;
     const uint32_t gq = (ngroups + kWaves - 1) / kWaves;
     const uint32_t gb = min(wave * gq, ngroups), ge = min(gb + gq, ngroups);
-    uint32_t mine = 0;
-    // a wave's quarter of up to 64 * kEmitKeep groups (1080p: 353) stays in registers with
-    // its counts for the write pass; a larger one is read and counted again there.  Max-t
-    // instances of the units with kEmitRegs only: it removes 1.9 M VALU per 1080p launch
-    // there, adds 0.4 M to a SAD launch and changes nothing without NMS.
-    constexpr uint32_t kEmitKeep = 6;
-    const bool in_regs = kEmitRegs && NMS == kNmsMaxThreshold &&
-                         ge - gb <= 64 * kEmitKeep;   // wave-uniform
-    uint4 kq[kEmitKeep];
-    uint32_t kc[kEmitKeep];
-    if (in_regs) {
-#pragma unroll
-        for (uint32_t j = 0; j < kEmitKeep; ++j) {
-            const uint32_t g = gb + 64 * j + lane;
-            kq[j] = g < ge ? keep4[g] : make_uint4(0u, 0u, 0u, 0u);
-            kc[j] = __popc(kq[j].x) + __popc(kq[j].y) + __popc(kq[j].z) + __popc(kq[j].w);
-            mine += kc[j];
-        }
-    } else {
+    uint32_t before = 0, total = list_total;
+    if (!from_list) {
+        uint32_t mine = 0;
         for (uint32_t g = gb + lane; g < ge; g += 64) {
             const uint4 q = keep4[g];
             mine += __popc(q.x) + __popc(q.y) + __popc(q.z) + __popc(q.w);
         }
-    }
-    const uint32_t wave_total = __builtin_amdgcn_readlane(wave_incl_scan(mine), 63);
-    if (lane == 0) wave_sum[wave] = wave_total;
-    __syncthreads();
-    uint32_t before = 0, total = 0;
+        const uint32_t wave_total = __builtin_amdgcn_readlane(wave_incl_scan(mine), 63);
+        if (lane == 0) wave_sum[wave] = wave_total;
+        __syncthreads();
+        total = 0;
 #pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-        const uint32_t v = wave_sum[w];
-        before += (uint32_t)w < wave ? v : 0u;
-        total += v;
+        for (int w = 0; w < kWaves; ++w) {
+            const uint32_t v = wave_sum[w];
+            before += (uint32_t)w < wave ? v : 0u;
+            total += v;
+        }
     }
     if (ablation_flags(P.flags) & kFlagNoEmit) return total;
-    uint8_t* slot = P.slots + (uint64_t)task * P.slot_bytes;
     const bool listed = total <= P.slot_bytes / 8;
     uint64_t dbase = 0;
     bool direct = P.direct != 0;
@@ -1407,8 +1465,25 @@ __device__ __forceinline__ uint32_t sweep_band(const BandParams& P, uint8_t* sme
         if (band == 0) P.frame_offsets[frame] = dbase;
         if (task == P.ntasks - 1) P.frame_offsets[frame + 1] = dbase + total;
     }
-    if (listed || direct) {
-        uint2* pts = reinterpret_cast<uint2*>(slot);
+    uint2* pts = reinterpret_cast<uint2*>(slot);
+    if ((listed || direct) && from_list) {
+        // Bounds: ranks are the raster ranks of the list's n distinct bitmap positions, so they
+        // are 0 .. n-1 with n <= kScoreListCap = 32 * kKillWords; a kept entry's idx counts the
+        // kept entries of lower rank, so idx < total <= n, and `listed` means the slot holds
+        // `total` points.  The direct write is under `cap`.
+        for (uint32_t i = tid; i < list_n; i += kThreads) {
+            const uint32_t e = sh.slist[i];
+            const uint32_t rank = (e & 0xfffu) - 1u, kw = kill[rank >> 5];
+            if ((kw >> (rank & 31u)) & 1u) continue;   // not output
+            const uint32_t idx = rank - kill[kKillWords + (rank >> 5)] -
+                                 (uint32_t)__popc(kw & ((1u << (rank & 31u)) - 1u));
+            uint32_t row, x;
+            pos_decode(sh.pc, e >> 12, row, x);
+            const uint2 pt = make_uint2(x, y0 - 1 + row);
+            if (listed) pts[idx] = pt;
+            if (direct && dbase + idx < P.cap) P.out[dbase + idx] = pt;
+        }
+    } else if (listed || direct) {
         uint32_t o = before;
         // one round of 64 groups: group g0 + lane, its 4 words q and their keypoint count c
         auto emit_round = [&](uint32_t g0, const uint4& q, uint32_t c) {
@@ -1434,19 +1509,29 @@ __device__ __forceinline__ uint32_t sweep_band(const BandParams& P, uint8_t* sme
                 ++idx;
             }
         };
-        if (in_regs) {
-#pragma unroll
-            for (uint32_t j = 0; j < kEmitKeep; ++j)
-                if (gb + 64 * j < ge) emit_round(gb + 64 * j, kq[j], kc[j]);
-        } else {
-            for (uint32_t g0 = gb; g0 < ge; g0 += 64) {
-                const uint32_t g = g0 + lane;
-                const uint4 q = g < ge ? keep4[g] : make_uint4(0u, 0u, 0u, 0u);
-                emit_round(g0, q, __popc(q.x) + __popc(q.y) + __popc(q.z) + __popc(q.w));
-            }
+        for (uint32_t g0 = gb; g0 < ge; g0 += 64) {
+            const uint32_t g = g0 + lane;
+            const uint4 q = g < ge ? keep4[g] : make_uint4(0u, 0u, 0u, 0u);
+            emit_round(g0, q, __popc(q.x) + __popc(q.y) + __popc(q.z) + __popc(q.w));
         }
     }
     if (!listed) {
+        // more points than the slot lists: the slot takes the keep-bitmap (the compaction
+        // expands it, and so does the host's recovery of a direct launch whose look-back
+        // timed out).  The list tier (narrow frames with tall forced bands get here) clears
+        // its killed keypoints' bits first, as the other tiers' NMS passes have done.
+        if (from_list) {
+            for (uint32_t i = tid; i < list_n; i += kThreads) {
+                const uint32_t e = sh.slist[i];
+                const uint32_t rank = (e & 0xfffu) - 1u;
+                if ((kill[rank >> 5] >> (rank & 31u)) & 1u) {
+                    uint32_t row, x;
+                    pos_decode(sh.pc, e >> 12, row, x);
+                    atomicAnd(&bitmap[row * nw + (x >> 5)], ~(1u << (x & 31)));
+                }
+            }
+            __syncthreads();
+        }
         uint32_t* words = reinterpret_cast<uint32_t*>(slot);
         for (uint32_t w = tid; w < nwords; w += kThreads) words[w] = keep[w];
     }

@@ -4,10 +4,6 @@
 #define FDF_SWEEP_RGB 0
 #define FDF_SWEEP_NS grey_lat
 #define FDF_SWEEP_TU_EXIT 1
-// The emit's register-resident write pass (FDF_SWEEP_TU_EMIT_REGS) makes these instances'
-// max-t kernels spill (512-528 bytes of scratch per lane; single frame max-t 16.8 -> 26.1 us):
-// off here.
-#define FDF_SWEEP_TU_EMIT_REGS 0
 #include "fdf_sweep_impl.h"
 
 namespace fdfk {
