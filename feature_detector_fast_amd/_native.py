@@ -48,7 +48,8 @@ EXPORTED_SYMBOLS = (
     "fdf_resize_frame", "fdf_pyramid_plan", "fdf_pyramid_taps", "fdf_pyramid_device",
     "fdf_harris_codes", "fdf_harris_device", "fdf_harris_points", "fdf_ransac_sample",
     "fdf_ransac_scratch_bytes", "fdf_ransac_device", "fdf_ransac_points",
-    "fdf_refine_scratch_bytes", "fdf_refine_device", "fdf_refine_points",
+    "fdf_refine_scratch_bytes", "fdf_refine_device", "fdf_refine_points", "fdf_warp_device",
+    "fdf_warp_frame", "fdf_model_invert",
 )
 
 
@@ -87,6 +88,8 @@ FDF_COORDS_F32 = 1
 FDF_MODEL_AFFINE = 0
 FDF_MODEL_HOMOGRAPHY = 1
 FDF_RANSAC_NONE = 0xFFFFFFFF
+FDF_BORDER_REPLICATE = 0
+FDF_BORDER_CONSTANT = 1
 
 
 class FdfError(RuntimeError):
@@ -287,6 +290,13 @@ def load():
     lib.fdf_refine_points.restype = ctypes.c_int
     lib.fdf_refine_points.argtypes = [vp, vp, vp, sz, sz, vp, vp, u32, u32, vp, ctypes.c_float,
                                       u32, vp, vp, vp]
+    lib.fdf_warp_device.restype = ctypes.c_int
+    lib.fdf_warp_device.argtypes = [vp, vp, u32, u32, u32, u64, vp, u64, vp, u32, u32, u64, u32,
+                                    u32, vp, vp]
+    lib.fdf_warp_frame.restype = ctypes.c_int
+    lib.fdf_warp_frame.argtypes = [vp, vp, u32, u32, sz, vp, vp, u32, u32, sz, u32, u32, vp]
+    lib.fdf_model_invert.restype = ctypes.c_int
+    lib.fdf_model_invert.argtypes = [vp, vp]
     del u8p
     _lib = lib
     return lib

@@ -382,6 +382,27 @@ struct ResizeParams {
 bool resize_fast_path(uint32_t src_w, uint32_t dst_w);
 hipError_t launch_resize(const ResizeParams& p, hipStream_t stream);
 
+// Exact bilinear warp by a 3 x 3 model per frame (fdf_warp.hip; fdf_warp_device).  The weights,
+// the rounding and the side limit are the resize's (kResizeOne, kResizeShift, kResizeMaxSide).
+constexpr int kWarpThreads = 256;
+constexpr uint32_t kWarpTileRows = 4;                          // destination rows a wave covers
+constexpr uint32_t kWarpReplicate = 0, kWarpConstant = 1;     // FDF_BORDER_*
+constexpr uint64_t kWarpModelBytes = 72;                      // nine doubles
+struct WarpParams {
+    const uint8_t* src;          // frame f at src + f * src_stride, src_w * src_h bytes
+    uint64_t src_stride;
+    uint8_t* dst;                // frame f at dst + f * dst_stride, dst_w * dst_h bytes
+    uint8_t* mask;               // laid out like dst, or NULL
+    uint64_t dst_stride;
+    const void* models;          // frame f's nine doubles at models + f * model_stride, 8-byte aligned
+    uint64_t model_stride;       // a multiple of 8, at least kWarpModelBytes
+    uint32_t n_frames, src_w, src_h, dst_w, dst_h;
+    uint32_t border, fill;       // kWarpReplicate / kWarpConstant; fill 0..255
+    uint32_t groups;             // ceil(dst_w / 4): a thread owns 4 destination columns of a row
+};
+// one kernel on `stream`: destination widths below 4 run a thread per pixel (the same integers)
+hipError_t launch_warp(const WarpParams& p, hipStream_t stream);
+
 // Brute-force Hamming matching of the 256-bit descriptors (fdf_match.hip; fdf_match_device,
 // fdf_match_filter_device).
 constexpr int kMatchThreads = 256;                    // queries of a workgroup pass

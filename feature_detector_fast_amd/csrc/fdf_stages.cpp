@@ -1,6 +1,7 @@
 // fdf_stages.cpp -- the C ABI of the stages behind the detector (extensions: the reference
 // returns points only): best-K selection, orientation, Harris response, steered BRIEF descriptors, box
-// smoothing, descriptor matching, RANSAC model estimation and the resize behind the scale pyramid.  Each has an asynchronous _device entry on the caller's stream and memory and a
+// smoothing, descriptor matching, RANSAC model estimation, the resize behind the scale pyramid and the warp by the estimated
+// models.  Each has an asynchronous _device entry on the caller's stream and memory and a
 // host convenience _points entry.  Of a context they use the device, the mutex and the
 // stream only: its workspace and retained result (fdf_fetch_last) are not touched.
 #include <algorithm>
@@ -831,6 +832,120 @@ int fdf_pyramid_device(fdf_ctx* ctx, const uint8_t* d_frames, uint32_t n_frames,
                                             d_taps + D.xtaps_offset, d_taps + D.ytaps_offset, s);
         if (e != hipSuccess) return FDF_ERR_DEVICE;
     }
+    return FDF_OK;
+}
+
+// ---- exact bilinear warp by a model per frame (fdf_warp.hip) ---------------------------------
+namespace {
+
+static_assert(FDF_BORDER_REPLICATE == fdfk::kWarpReplicate &&
+                  FDF_BORDER_CONSTANT == fdfk::kWarpConstant &&
+                  offsetof(fdf_model, h) == 0 && sizeof(fdf_model) == 88,
+              "the kernels' constants are the header's; an fdf_model starts with its matrix");
+
+// What fdf_warp_device checks of its values (not of its pointers): the resize's shapes and
+// strides, then the border, the fill and the model stride.
+int check_warp(uint32_t n_frames, uint32_t src_w, uint32_t src_h, uint64_t src_stride_bytes,
+               uint32_t dst_w, uint32_t dst_h, uint64_t dst_stride_bytes,
+               uint64_t model_stride_bytes, uint32_t border, uint32_t fill, uint64_t* src_stride,
+               uint64_t* dst_stride) {
+    const int rc = check_resize(n_frames, src_w, src_h, src_stride_bytes, dst_w, dst_h,
+                                dst_stride_bytes, src_stride, dst_stride);
+    if (rc == FDF_ERR_SIZE || n_frames > 65535u) return rc;
+    if (border > FDF_BORDER_CONSTANT || fill > 255u ||
+        model_stride_bytes < fdfk::kWarpModelBytes || model_stride_bytes % 8)
+        return FDF_ERR_ARG;
+    return rc;
+}
+
+hipError_t warp_enqueue(const uint8_t* d_src, uint32_t n_frames, uint32_t src_w, uint32_t src_h,
+                        uint64_t src_stride, const void* d_models, uint64_t model_stride,
+                        uint8_t* d_dst, uint32_t dst_w, uint32_t dst_h, uint64_t dst_stride,
+                        uint32_t border, uint32_t fill, uint8_t* d_mask, hipStream_t s) {
+    fdfk::WarpParams p{};
+    p.src = d_src;
+    p.src_stride = src_stride;
+    p.dst = d_dst;
+    p.mask = d_mask;
+    p.dst_stride = dst_stride;
+    p.models = d_models;
+    p.model_stride = model_stride;
+    p.n_frames = n_frames;
+    p.src_w = src_w;
+    p.src_h = src_h;
+    p.dst_w = dst_w;
+    p.dst_h = dst_h;
+    p.border = border;
+    p.fill = fill;
+    p.groups = (dst_w + 3) / 4;
+    return fdfk::launch_warp(p, s);
+}
+
+}  // namespace
+
+int fdf_warp_device(fdf_ctx* ctx, const uint8_t* d_src, uint32_t n_frames, uint32_t src_w,
+                    uint32_t src_h, uint64_t src_frame_stride_bytes, const void* d_models,
+                    uint64_t model_stride_bytes, uint8_t* d_dst, uint32_t dst_w, uint32_t dst_h,
+                    uint64_t dst_frame_stride_bytes, uint32_t border, uint32_t fill,
+                    uint8_t* d_mask, void* stream) {
+    if (!ctx) return FDF_ERR_ARG;
+    uint64_t ss = 0, ds = 0;
+    const int rc = check_warp(n_frames, src_w, src_h, src_frame_stride_bytes, dst_w, dst_h,
+                              dst_frame_stride_bytes, model_stride_bytes, border, fill, &ss, &ds);
+    if (rc == FDF_ERR_SIZE || n_frames > 65535u) return rc;
+    if (n_frames == 0 && rc == FDF_OK) return FDF_OK;
+    if (rc || !d_src || !d_dst || !d_models || reinterpret_cast<uintptr_t>(d_models) % 8)
+        return FDF_ERR_ARG;
+    DeviceGuard guard(ctx->device);
+    return status_of(warp_enqueue(d_src, n_frames, src_w, src_h, ss, d_models, model_stride_bytes,
+                                  d_dst, dst_w, dst_h, ds, border, fill, d_mask,
+                                  reinterpret_cast<hipStream_t>(stream)));
+}
+
+int fdf_warp_frame(fdf_ctx* ctx, const uint8_t* data, uint32_t width, uint32_t height,
+                   size_t stride_bytes, const double h[9], uint8_t* out, uint32_t dst_w,
+                   uint32_t dst_h, size_t out_stride_bytes, uint32_t border, uint32_t fill,
+                   uint8_t* out_mask) {
+    if (!ctx) return FDF_ERR_ARG;
+    uint64_t ss = 0, ds = 0;
+    const int rc = check_warp(1, width, height, 0, dst_w, dst_h, 0, fdfk::kWarpModelBytes, border,
+                              fill, &ss, &ds);
+    if (rc) return rc;
+    if (!data || !h || !out || stride_bytes < width || out_stride_bytes < dst_w) return FDF_ERR_ARG;
+    double model[9];                                     // an asynchronous copy's source
+    std::copy(h, h + 9, model);
+    Arena a(ctx);
+    const auto d_src = a.part<uint8_t>(ss);
+    const auto d_dst = a.part<uint8_t>(ds);
+    const auto d_mask = a.part<uint8_t>(out_mask ? ds : 0);
+    const auto d_model = a.part<double>(9);
+    if (a.open() != FDF_OK) return FDF_ERR_ALLOC;
+    a.upload_frame(d_src, data, width, height, stride_bytes);
+    a.upload(d_model, model);
+    if (a.ok())
+        a.note(warp_enqueue(a.at(d_src), 1, width, height, ss, a.at(d_model),
+                            fdfk::kWarpModelBytes, a.at(d_dst), dst_w, dst_h, ds, border, fill,
+                            out_mask ? a.at(d_mask) : nullptr, ctx->stream));
+    a.download_frame(out, d_dst, dst_w, dst_h, out_stride_bytes);
+    if (out_mask) a.download_frame(out_mask, d_mask, dst_w, dst_h, out_stride_bytes);
+    return a.close();
+}
+
+int fdf_model_invert(const double h[9], double out[9]) {
+#pragma clang fp contract(off)
+    if (!h || !out) return FDF_ERR_ARG;
+    // the adjugate, each product and each difference rounded once
+    const double c[9] = {
+        h[4] * h[8] - h[5] * h[7], h[2] * h[7] - h[1] * h[8], h[1] * h[5] - h[2] * h[4],
+        h[5] * h[6] - h[3] * h[8], h[0] * h[8] - h[2] * h[6], h[2] * h[3] - h[0] * h[5],
+        h[3] * h[7] - h[4] * h[6], h[1] * h[6] - h[0] * h[7], h[0] * h[4] - h[1] * h[3]};
+    double r[9];
+    for (int k = 0; k < 8; ++k) {
+        r[k] = c[k] / c[8];
+        if (!std::isfinite(r[k])) return FDF_ERR_ARG;
+    }
+    r[8] = 1.0;
+    std::copy(r, r + 9, out);
     return FDF_OK;
 }
 

@@ -1141,7 +1141,121 @@ def resize_array(img, shape, device=0):
     return out
 
 
-PyramidLevel = collections.namedtuple(
+_BORDERS = {"replicate": _native.FDF_BORDER_REPLICATE, "constant": _native.FDF_BORDER_CONSTANT}
+
+
+def _border_fill(border, fill):
+    """(FDF_BORDER_*, fill) of a warp."""
+    if border not in _BORDERS:
+        raise ValueError('border must be "replicate" or "constant"')
+    fill = int(fill)
+    if not 0 <= fill <= 255:
+        raise ValueError("fill must be in 0..255")
+    return _BORDERS[border], fill
+
+
+def _host_model(h):
+    """Nine float64 numbers from nine numbers, a 3 x 3 array, a MODEL_DTYPE record or what
+    estimate_model / refine_model return (their record is used)."""
+    if isinstance(h, tuple) and len(h) in (3, 4) and isinstance(h[2], np.void):
+        h = h[2]
+    a = np.asarray(h)
+    if a.dtype == MODEL_DTYPE and a.size == 1:
+        return np.array(a.reshape(-1)[0]["h"], dtype=np.float64)
+    if a.dtype.kind in "fiu" and a.size == 9:
+        return np.ascontiguousarray(a, dtype=np.float64).reshape(9).copy()
+    raise TypeError("a model is nine numbers, a (3, 3) array, a MODEL_DTYPE record or "
+                    "estimate_model's result")
+
+
+def model_invert(h):
+    """The model that warps the other way (fdf_model_invert; host only, no device): the adjugate
+    of ``h`` normalised to [2, 2] = 1 as a (3, 3) float64 array.  FdfError(FDF_ERR_ARG) for a
+    singular model."""
+    m = _host_model(h)
+    out = np.zeros(9, dtype=np.float64)
+    check(_native.load().fdf_model_invert(m.ctypes.data, out.ctypes.data), "fdf_model_invert")
+    return out.reshape(3, 3)
+
+
+def warp_device(frames, models, out, border="replicate", fill=0, mask=None, stream=None,
+                device=None):
+    """Exact bilinear warp on the device (fdf_warp_device): frame f of ``frames`` (F, H, W) is
+    resampled into frame f of ``out`` (F, h, w) by model f, which maps a pixel of ``out`` to a
+    position in ``frames`` -- ransac_device's / refine_device's models of (query, train) warp
+    the train frames onto the query frames as they are.  ``models`` is their (F, 11) float64
+    record tensor or an (F, 9) float64 tensor of row-major matrices, contiguous.  Both frame
+    tensors are uint8 with contiguous frames any number of bytes apart (each its own); the bytes
+    between output frames are not written; they must not overlap.  ``border``: "replicate", or
+    "constant" with the value ``fill``; pixels without a position (w <= 0, NaN, beyond 2^19
+    pixels) get ``fill`` in both.  ``mask`` (optional, uint8, the shape and strides of ``out``)
+    gets 1 where the position lies inside the source frame.  Asynchronous on ``stream``
+    (default: torch's current stream)."""
+    import torch
+
+    _check_frames(torch, frames)
+    _check_frames(torch, out, "out")
+    f, sh, sw = frames.shape
+    of, dh, dw = out.shape
+    if of != f:
+        raise ValueError("frames and out must hold the same number of frames")
+    if f > 65535:
+        raise ValueError("at most 65535 frames")
+    for h, w, name in ((sh, sw, "frames"), (dh, dw, "out")):
+        if h < 1 or w < 1 or h * w > _MAX_PIXELS:
+            raise ValueError(f"{name}: 1 <= width * height <= 2^31 - 256 pixels")
+    if sh > _MAX_SIDE or sw > _MAX_SIDE:
+        raise ValueError("a source side is at most 65535 pixels")
+    if models.dtype != torch.float64 or models.dim() != 2 or models.shape[1] not in (9, 11) or \
+            models.shape[0] < f or not models.is_contiguous():
+        raise ValueError("models must be a contiguous (F, 11) or (F, 9) float64 tensor")
+    border, fill = _border_fill(border, fill)
+    tensors = [frames, models, out]
+    if mask is not None:
+        _check_frames(torch, mask, "mask")
+        if mask.shape != out.shape or (f > 1 and mask.stride(0) != out.stride(0)):
+            raise ValueError("mask must have the shape and frame stride of out")
+        tensors.append(mask)
+    _check_one_device("warp_device", tensors)
+    if f:
+        spans = [(t.data_ptr(), t.data_ptr() + (f - 1) * t.stride(0) + t.shape[1] * t.shape[2])
+                 for t in tensors if t is not models]
+        for i, (a0, a1) in enumerate(spans):
+            for b0, b1 in spans[i + 1:]:
+                if a0 < b1 and b0 < a1:
+                    raise ValueError("frames, out and mask must not overlap")
+    dev, stream = _device_stream(torch, frames, device, stream)
+    out_ptr, _, _, _, out_stride = _frame_args(out)
+    rc = _native.load().fdf_warp_device(
+        context(dev).handle, *_frame_args(frames), models.data_ptr(), 8 * models.shape[1],
+        out_ptr, dw, dh, out_stride, border, fill,
+        mask.data_ptr() if mask is not None else None, ctypes.c_void_p(stream.cuda_stream))
+    check(rc, "fdf_warp_device")
+
+
+def warp_array(img, h, shape=None, border="replicate", fill=0, mask=False, device=0):
+    """One host image warped by the model ``h`` into ``shape`` = (height, width) (default: the
+    image's) (fdf_warp_frame): a (height, width) uint8 array, and with ``mask`` the pair (array,
+    bool mask of the pixels whose position lies inside the image).  ``h`` maps a pixel of the
+    result to a position in ``img``: nine numbers, a (3, 3) array, or what estimate_model /
+    refine_model return."""
+    arr = _as_pixels(img)
+    m = _host_model(h)
+    sh, sw = arr.shape
+    dh, dw = _dst_shape(arr.shape if shape is None else shape)
+    if sh < 1 or sw < 1 or sh > _MAX_SIDE or sw > _MAX_SIDE or sh * sw > _MAX_PIXELS:
+        raise ValueError("the image must have sides in 1..65535 and at most 2^31 - 256 pixels")
+    border, fill = _border_fill(border, fill)
+    out = np.zeros((dh, dw), dtype=np.uint8)
+    inside = np.zeros((dh, dw), dtype=np.uint8) if mask else None
+    rc = _native.load().fdf_warp_frame(
+        context(device).handle, arr.ctypes.data, sw, sh, arr.strides[0], m.ctypes.data,
+        out.ctypes.data, dw, dh, dw, border, fill, inside.ctypes.data if mask else None)
+    check(rc, "fdf_warp_frame")
+    return (out, inside.astype(bool)) if mask else out
+
+
+PyramidLevel =collections.namedtuple(
     "PyramidLevel", "width height frame_stride_bytes offset_bytes xtaps_offset ytaps_offset")
 
 
@@ -1902,6 +2016,7 @@ __all__ = ["NORTH", "EAST", "SOUTH", "WEST", "circle", "calculate_offsets", "con
            "MODEL_DTYPE", "RANSAC_NONE", "ransac_sample", "ransac_scratch_bytes", "ransac_device",
            "unpack_models", "estimate_model",
            "refine_scratch_bytes", "refine_device", "refine_model",
+           "warp_device", "warp_array", "model_invert",
            "detect_rgb_array", "detector_rgb", "rgb_to_luma", "detect_device_rgb",
            "score_rings", "score_rings_device", "keypoint_score_max_threshold",
            "keypoint_score_sum_abs_difference", "NonMaximalSuppression"]

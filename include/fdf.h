@@ -39,7 +39,8 @@ extern "C" {
  * fdf_resize_device, fdf_resize_frame, fdf_pyramid_plan, fdf_pyramid_taps and
  * fdf_pyramid_device, and fdf_harris_codes, fdf_harris_device and fdf_harris_points, and
  * fdf_ransac_sample, fdf_ransac_scratch_bytes, fdf_ransac_device and fdf_ransac_points, and
- * fdf_refine_scratch_bytes, fdf_refine_device and fdf_refine_points. */
+ * fdf_refine_scratch_bytes, fdf_refine_device and fdf_refine_points, and fdf_warp_device,
+ * fdf_warp_frame and fdf_model_invert. */
 #define FDF_ABI_VERSION 6
 
 /* Status codes.  Shapes the reference maps to an empty Vec return FDF_OK with 0 points. */
@@ -961,6 +962,93 @@ int fdf_pyramid_device(fdf_ctx* ctx, const uint8_t* d_frames, uint32_t n_frames,
                        uint64_t frame_stride_bytes, const fdf_pyramid_level* levels,
                        uint32_t n_levels, uint8_t* d_pyramid, const uint32_t* d_taps,
                        void* stream);
+
+/*
+ * Exact bilinear warp of frames by a 3 x 3 model per frame (extension: what callers estimate a
+ * model for -- warpAffine / warpPerspective for stabilisation, registration before differencing,
+ * mosaicking).  Like the resize it is integer-exact after one fixed sequence of binary64 steps,
+ * so a numpy restatement reproduces it bit for bit.  These are not OpenCV's bits.
+ *
+ * Direction.  The model maps a destination pixel to a source position (inverse mapping).  That
+ * is what fdf_ransac_device / fdf_refine_device produce for query frame A and train frame B:
+ * warping B with the model as estimated gives B registered onto A, nothing is inverted.  "Frame
+ * f against frame f + 1 of one batch" is d_src = frames + stride, n_frames = F - 1.
+ *
+ * Models.  Frame f's nine doubles h0..h8 (row-major) are the first 72 bytes at d_models + f *
+ * model_stride_bytes; the array is 8-byte aligned and the stride a multiple of 8 and at least 72:
+ * 88 is an fdf_model array as the estimator leaves it, 72 is packed matrices.  h8 is used as
+ * given, not assumed to be 1; an affine model needs no special path (h6 = h7 = 0).
+ *
+ * Position of destination pixel (x, y), x in [0, dst_w), y in [0, dst_h), both converted to
+ * double; each step is one IEEE binary64 operation, never fused:
+ *   P = (h0 x + h1 y) + h2,  Q = (h3 x + h4 y) + h5,  w = (h6 x + h7 y) + h8,
+ *   sx = P / w,  sy = Q / w,
+ *   FX = floor(sx * 2048.0 + 0.5),  FY = floor(sy * 2048.0 + 0.5).
+ * The pixel is valid iff w > 0 and -2^30 <= FX <= 2^30 and -2^30 <= FY <= 2^30 (every comparison
+ * is false for a NaN).  For a valid pixel X = (int32)FX, ix = X >> 11 (arithmetic shift) and
+ * qx = X & 2047, the same for y; the four taps are (ix + a, iy + b) with a, b in {0, 1} and the
+ * weights w_0 = 2048 - q, w_1 = q of each axis.
+ *
+ * Pixel.  A valid pixel is out = (sum over a, b of wy_b * wx_a * T(ix + a, iy + b) + 2^21) >> 22,
+ * the resize rule's sum (below 2^30, one rounding).  T is set by `border`:
+ *   FDF_BORDER_REPLICATE: T(cx, cy) = I(clamp(cx, 0, W - 1), clamp(cy, 0, H - 1)), the border of
+ *     every other stage;
+ *   FDF_BORDER_CONSTANT: a tap outside the frame has the value `fill` (0..255).
+ * An invalid pixel is `fill` in both modes: a frame whose model is all zero (no model,
+ * hypothesis == FDF_RANSAC_NONE) or holds NaNs comes out as a constant `fill` frame.
+ *
+ * Mask (optional d_mask, laid out like d_dst).  The byte is 1 iff the pixel is valid and
+ * 0 <= X <= (W - 1) * 2048 and 0 <= Y <= (H - 1) * 2048 (the position lies inside the source
+ * frame), and 0 otherwise.
+ *
+ * So the identity model is a copy, an integer translation is an exact shift,
+ * h = 1 0 0.5 0 1 0 0 0 1 gives (I(x) + I(x + 1) + 1) >> 1 and a constant frame stays constant
+ * under replicate.
+ *
+ * Example.  The 4 x 4 source I(x, y) = 16 (4 y + x), h = 0.75 0.25 0.5 -0.25 0.75 1 0.0625 0 1,
+ * a 4 x 4 destination, constant border, fill 255: the rows are 72 64 57 51 / 124 113 103 94 /
+ * 176 162 149 138 / 223 211 196 182 and the mask is all ones except the first byte of the last
+ * row.
+ *
+ * fdf_warp_device: asynchronous on `stream` (NULL = the HIP null stream); like fdf_resize_device
+ * it takes no context lock and uses no context workspace, it only binds the context's device;
+ * nothing is allocated and nothing returns to the host.  Frames may be any number of bytes apart
+ * on either side and have any alignment; the mask's frames lie dst_frame_stride_bytes apart too;
+ * gap bytes are never written; source and destination must not overlap.  Whatever the models
+ * hold (NaN, infinities, 1e300) no access leaves the frames: tap indices are clamped before use
+ * and pixel accesses go through buffer resources of exactly a frame's bytes.  FDF_ERR_ARG,
+ * synchronously and with nothing launched: n_frames > 65535, a frame stride below width * height
+ * when n_frames > 1, a model stride below 72 or no multiple of 8, border > 1, fill > 255; and,
+ * unless n_frames == 0 (FDF_OK, nothing written): a NULL pointer (all but d_mask), models that
+ * are not 8-byte aligned.  FDF_ERR_SIZE: a zero dimension, width * height above 2^31 - 256 on
+ * either side, a source side above 65535.
+ *
+ * fdf_warp_frame: one host frame (rows stride_bytes apart) to one host frame and an optional
+ * mask (rows out_stride_bytes apart, both), synchronous.  Copies through device buffers allocated
+ * and freed by the call and runs the same kernel; the context's workspace and retained result
+ * are untouched, so fdf_fetch_last stays valid.
+ *
+ * fdf_model_invert: host only, no context; the model that warps the other way (A onto B): the
+ * adjugate normalised to out[8] = 1, one fixed sequence with each step rounded once:
+ *   c0 = h4 h8 - h5 h7,  c1 = h2 h7 - h1 h8,  c2 = h1 h5 - h2 h4,
+ *   c3 = h5 h6 - h3 h8,  c4 = h0 h8 - h2 h6,  c5 = h2 h3 - h0 h5,
+ *   c6 = h3 h7 - h4 h6,  c7 = h1 h6 - h0 h7,  c8 = h0 h4 - h1 h3,
+ *   out_k = c_k / c8 for k < 8,  out_8 = 1.
+ * FDF_ERR_ARG, with `out` untouched: a NULL pointer, or an out_k that is not finite (a singular
+ * matrix).  `out` may be `h`.
+ */
+#define FDF_BORDER_REPLICATE 0u
+#define FDF_BORDER_CONSTANT 1u
+int fdf_warp_device(fdf_ctx* ctx, const uint8_t* d_src, uint32_t n_frames, uint32_t src_w,
+                    uint32_t src_h, uint64_t src_frame_stride_bytes, const void* d_models,
+                    uint64_t model_stride_bytes, uint8_t* d_dst, uint32_t dst_w, uint32_t dst_h,
+                    uint64_t dst_frame_stride_bytes, uint32_t border, uint32_t fill,
+                    uint8_t* d_mask, void* stream);
+int fdf_warp_frame(fdf_ctx* ctx, const uint8_t* data, uint32_t width, uint32_t height,
+                   size_t stride_bytes, const double h[9], uint8_t* out, uint32_t dst_w,
+                   uint32_t dst_h, size_t out_stride_bytes, uint32_t border, uint32_t fill,
+                   uint8_t* out_mask);
+int fdf_model_invert(const double h[9], double out[9]);
 
 /*
  * Streaming host pipeline (extension; the reference's callers detect on one

@@ -22,6 +22,7 @@
 //   (none: ... and fit a model)      --                   fdf::estimate_model(q_points, t_points, matches, ...)
 //   (none: ... and refine it)        --                   fdf::refine_model(q_points, t_points, matches, estimate, ...)
 //   (none: ... over a scale pyramid) --                   fdf::resize, fdf::pyramid_plan, fdf::build_pyramid
+//   (none: ... and warp by the model) --                  fdf::warp, fdf::model_invert
 //
 // Where the reference panics (n < 9, n > 16, degenerate sizes) these throw fdf::Error.
 // Each thread lazily owns one device context per HIP device (device 0 unless
@@ -465,6 +466,36 @@ inline std::vector<Image> build_pyramid(const GrayView& img, uint32_t n_levels, 
 inline std::vector<Image> build_pyramid(const GrayView& img, uint32_t n_levels = 8,
                                         uint32_t num = 6, uint32_t den = 5) {
     return build_pyramid(img, n_levels, num, den, thread_context());
+}
+
+// Exact bilinear warp by a 3 x 3 model (extension, fdf_warp_frame; include/fdf.h has the rule).
+// `h` (row-major, ModelEstimate::model.h as estimated) maps a destination pixel to a source
+// position: warping the train frame with it registers it onto the query frame.  `mask`
+// (optional) gets 1 where the position lies inside the source frame.
+inline Image warp(const GrayView& img, const double (&h)[9], uint32_t dst_w, uint32_t dst_h,
+                  uint32_t border, uint32_t fill, std::vector<uint8_t>* mask, Context& ctx) {
+    Image out;
+    out.width = dst_w;
+    out.height = dst_h;
+    out.pixels.resize((size_t)dst_w * dst_h);
+    if (mask) mask->assign((size_t)dst_w * dst_h, 0);
+    check(fdf_warp_frame(ctx.get(), img.data, img.width, img.height, img.stride, h,
+                         out.pixels.data(), dst_w, dst_h, dst_w, border, fill,
+                         mask ? mask->data() : nullptr),
+          "fdf_warp_frame");
+    return out;
+}
+inline Image warp(const GrayView& img, const double (&h)[9], uint32_t dst_w, uint32_t dst_h,
+                  uint32_t border = FDF_BORDER_REPLICATE, uint32_t fill = 0,
+                  std::vector<uint8_t>* mask = nullptr) {
+    return warp(img, h, dst_w, dst_h, border, fill, mask, thread_context());
+}
+
+// The model that warps the other way (fdf_model_invert); throws FDF_ERR_ARG for a singular one.
+inline std::array<double, 9> model_invert(const double (&h)[9]) {
+    std::array<double, 9> out{};
+    check(fdf_model_invert(h, out.data()), "fdf_model_invert");
+    return out;
 }
 
 inline std::vector<Point> detect(const GrayView& img, const Config& config) {
