@@ -49,7 +49,8 @@ EXPORTED_SYMBOLS = (
     "fdf_harris_codes", "fdf_harris_device", "fdf_harris_points", "fdf_ransac_sample",
     "fdf_ransac_scratch_bytes", "fdf_ransac_device", "fdf_ransac_points",
     "fdf_refine_scratch_bytes", "fdf_refine_device", "fdf_refine_points", "fdf_warp_device",
-    "fdf_warp_frame", "fdf_model_invert",
+    "fdf_warp_frame", "fdf_model_invert", "fdf_track_device", "fdf_track_frames",
+    "fdf_track_map_position", "fdf_track_map_displacement",
 )
 
 
@@ -85,6 +86,7 @@ FDF_MATCH_NONE = 0xFFFFFFFF
 FDF_MATCH_NO_DISTANCE = 0xFFFF
 FDF_COORDS_U32 = 0
 FDF_COORDS_F32 = 1
+FDF_COORDS_Q11 = 2
 FDF_MODEL_AFFINE = 0
 FDF_MODEL_HOMOGRAPHY = 1
 FDF_RANSAC_NONE = 0xFFFFFFFF
@@ -297,6 +299,18 @@ def load():
     lib.fdf_warp_frame.argtypes = [vp, vp, u32, u32, sz, vp, vp, u32, u32, sz, u32, u32, vp]
     lib.fdf_model_invert.restype = ctypes.c_int
     lib.fdf_model_invert.argtypes = [vp, vp]
+    i64 = ctypes.c_int64
+    lib.fdf_track_map_position.restype = ctypes.c_int
+    lib.fdf_track_map_position.argtypes = [i64, u32, u32, ctypes.POINTER(i64)]
+    lib.fdf_track_map_displacement.restype = ctypes.c_int
+    lib.fdf_track_map_displacement.argtypes = [i64, u32, u32, ctypes.POINTER(i64)]
+    lib.fdf_track_device.restype = ctypes.c_int
+    lib.fdf_track_device.argtypes = [vp, vp, vp, u32, vp, vp, u32, u32, u64, vp, u32, vp, u32, u64,
+                                     vp, vp, vp, u32, u32, u32, ctypes.c_float, vp, vp, vp, vp, vp,
+                                     vp, vp]
+    lib.fdf_track_frames.restype = ctypes.c_int
+    lib.fdf_track_frames.argtypes = [vp, vp, vp, u32, u32, sz, vp, u32, sz, vp, u32, u32, u32, u32,
+                                     u32, u32, ctypes.c_float, vp, vp, vp, vp, vp]
     del u8p
     _lib = lib
     return lib

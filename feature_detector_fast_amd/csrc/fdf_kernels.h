@@ -403,6 +403,63 @@ struct WarpParams {
 // one kernel on `stream`: destination widths below 4 run a thread per pixel (the same integers)
 hipError_t launch_warp(const WarpParams& p, hipStream_t stream);
 
+// Pyramidal Lucas-Kanade tracking of keypoints (fdf_track.hip; fdf_track_device).  Positions are
+// int32 in units of 1 / kResizeOne pixel ("Q11"); the sample keeps 5 fractional bits.
+constexpr int kTrackThreads = 256;                    // 4 waves, one point each per pass
+constexpr uint32_t kTrackMaxRadius = 15;              // (2 r + 1)^2 <= 16 window pixels per lane
+constexpr uint32_t kTrackMaxSlots = 16;
+constexpr uint32_t kTrackMaxIters = 64;
+constexpr uint32_t kTrackMaxLevels = 32;
+constexpr uint32_t kTrackSampleShift = 17;            // two weights of 11 bits less 5 kept bits
+constexpr uint32_t kTrackSampleHalf = 1u << (kTrackSampleShift - 1);
+constexpr double kTrackStepScale = 65536.0;           // 32 (the sample's bits) * 2048
+constexpr double kTrackStepLimit = 0x1p20;            // |FDX|, |FDY| of an accepted step
+constexpr uint32_t kTrackU32 = 0, kTrackQ11 = 2;      // FDF_COORDS_U32, FDF_COORDS_Q11
+constexpr uint32_t kTrackSkipped = 0, kTrackTracked = 1, kTrackEigen = 2, kTrackLeft = 3,
+                   kTrackStep = 4;                    // d_info reasons
+constexpr uint32_t kTrackNoErr = 0xffffffffu;
+
+// The level maps of include/fdf.h (all int64; floor division).
+__host__ __device__ inline int64_t track_floor_div(int64_t a, int64_t b) {   // b > 0
+    const int64_t q = a / b;
+    return a % b < 0 ? q - 1 : q;
+}
+__host__ __device__ inline int64_t track_map_pos(int64_t x, int64_t len0, int64_t lenl) {
+    const int64_t v = track_floor_div((x + 1024) * lenl * 2 + len0, 2 * len0) - 1024;
+    const int64_t hi = (lenl - 1) * (int64_t)kResizeOne;
+    return v < 0 ? 0 : v > hi ? hi : v;
+}
+__host__ __device__ inline int64_t track_map_disp(int64_t d, int64_t from, int64_t to) {
+    return track_floor_div(2 * d * to + from, 2 * from);
+}
+
+struct TrackLevel {
+    const uint8_t* prev;         // the level of the call's frame 0 in the previous set
+    const uint8_t* next;         // ... in the next set
+    uint64_t prev_stride;        // bytes between the level's frames
+    uint64_t next_stride;
+    uint32_t width, height;
+};
+struct TrackParams {
+    TrackLevel levels[kTrackMaxLevels];
+    uint32_t n_levels, n_frames;
+    const void* pts;             // `cap` points: 2 x u32 pixels (kTrackU32) or 2 x int32 Q11
+    const uint64_t* offs;        // n_frames + 1 entries
+    uint64_t cap;
+    const uint8_t* keep;         // `cap` flags, or NULL: all ones
+    const int2* guess;           // `cap` Q11 starting positions in the next frame, or NULL
+    uint32_t coords, radius, max_iters, eps;
+    double tau;                  // (min_eig * n) * 2^20
+    int2* next_q11;              // `cap`
+    float2* next_f32;            // `cap`, or NULL
+    uint8_t* status;             // `cap`
+    uint32_t* err;               // `cap`, or NULL
+    uint32_t* info;              // `cap`, or NULL
+    uint2* matches;              // `cap` fdf_match, or NULL
+};
+// one kernel on `stream`: `chunks` workgroups per frame share the frame's points
+hipError_t launch_track(const TrackParams& p, uint32_t chunks, hipStream_t stream);
+
 // Brute-force Hamming matching of the 256-bit descriptors (fdf_match.hip; fdf_match_device,
 // fdf_match_filter_device).
 constexpr int kMatchThreads = 256;                    // queries of a workgroup pass

@@ -1,7 +1,7 @@
 // fdf_stages.cpp -- the C ABI of the stages behind the detector (extensions: the reference
 // returns points only): best-K selection, orientation, Harris response, steered BRIEF descriptors, box
-// smoothing, descriptor matching, RANSAC model estimation, the resize behind the scale pyramid and the warp by the estimated
-// models.  Each has an asynchronous _device entry on the caller's stream and memory and a
+// smoothing, descriptor matching, RANSAC model estimation, the resize behind the scale pyramid, the warp by the estimated
+// models and Lucas-Kanade tracking.  Each has an asynchronous _device entry on the caller's stream and memory and a
 // host convenience _points entry.  Of a context they use the device, the mutex and the
 // stream only: its workspace and retained result (fdf_fetch_last) are not touched.
 #include <algorithm>
@@ -947,6 +947,212 @@ int fdf_model_invert(const double h[9], double out[9]) {
     r[8] = 1.0;
     std::copy(r, r + 9, out);
     return FDF_OK;
+}
+
+// ---- pyramidal Lucas-Kanade tracking (fdf_track.hip) -----------------------------------------
+
+int fdf_track_map_position(int64_t x, uint32_t len0, uint32_t len_l, int64_t* out) {
+    if (!out || len0 == 0 || len0 > 65535u || len_l == 0 || len_l > 65535u || x > (1ll << 28) ||
+        x < -(1ll << 28))
+        return FDF_ERR_ARG;
+    *out = fdfk::track_map_pos(x, len0, len_l);
+    return FDF_OK;
+}
+
+int fdf_track_map_displacement(int64_t d, uint32_t len_from, uint32_t len_to, int64_t* out) {
+    if (!out || len_from == 0 || len_from > 65535u || len_to == 0 || len_to > 65535u ||
+        d > (1ll << 28) || d < -(1ll << 28))
+        return FDF_ERR_ARG;
+    *out = fdfk::track_map_disp(d, len_from, len_to);
+    return FDF_OK;
+}
+
+namespace {
+
+static_assert(FDF_COORDS_U32 == fdfk::kTrackU32 && FDF_COORDS_Q11 == fdfk::kTrackQ11,
+              "the kernel's constants are the header's");
+
+// What the tracker checks of its values (not of its pointers), in the order of the header.
+int check_track(uint32_t n_frames, uint32_t prev_first, uint32_t next_first,
+                uint64_t frame_stride_bytes, const fdf_pyramid_level* levels, uint32_t n_levels,
+                uint32_t coords, uint32_t radius, uint32_t max_iters, float min_eig) {
+    if (radius == 0 || radius > fdfk::kTrackMaxRadius || max_iters == 0 ||
+        max_iters > fdfk::kTrackMaxIters || !(min_eig >= 0.0f) || !std::isfinite(min_eig) ||
+        (coords != FDF_COORDS_U32 && coords != FDF_COORDS_Q11) || n_frames > 65535u || !levels ||
+        n_levels == 0 || n_levels > fdfk::kTrackMaxLevels)
+        return FDF_ERR_ARG;
+    for (uint32_t l = 0; l < n_levels; ++l) {
+        const uint64_t bytes = (uint64_t)levels[l].width * levels[l].height;
+        if (bytes == 0 || levels[l].width > fdfk::kResizeMaxSide ||
+            levels[l].height > fdfk::kResizeMaxSide || bytes > fdfk::kOrientMaxPixels)
+            return FDF_ERR_SIZE;
+    }
+    // frames up to first + n_frames are addressed on either side
+    const uint64_t addressed = (uint64_t)std::max(prev_first, next_first) + n_frames;
+    if (n_frames != 0 && addressed > 1)
+        for (uint32_t l = 0; l < n_levels; ++l) {
+            const uint64_t stride = l == 0 ? frame_stride_bytes : levels[l].frame_stride_bytes;
+            if (stride < (uint64_t)levels[l].width * levels[l].height) return FDF_ERR_ARG;
+        }
+    return FDF_OK;
+}
+
+struct TrackOutputs {
+    int32_t* q11;
+    float* f32;
+    uint8_t* status;
+    uint32_t* err;
+    uint32_t* info;
+    fdf_match* matches;
+};
+
+// The launch of fdf_track_device / fdf_track_frames (arguments already validated).
+hipError_t track_enqueue(const uint8_t* d_prev_frames, const uint8_t* d_prev_pyramid,
+                         uint32_t prev_first, const uint8_t* d_next_frames,
+                         const uint8_t* d_next_pyramid, uint32_t next_first, uint32_t n_frames,
+                         uint64_t frame_stride_bytes, const fdf_pyramid_level* levels,
+                         uint32_t n_levels, const void* d_points, uint32_t coords, uint64_t cap,
+                         const uint64_t* d_offsets, const uint8_t* d_keep, const int32_t* d_guess,
+                         uint32_t radius, uint32_t max_iters, uint32_t eps, float min_eig,
+                         const TrackOutputs& o, hipStream_t s) {
+#pragma clang fp contract(off)
+    fdfk::TrackParams p{};
+    for (uint32_t l = 0; l < n_levels; ++l) {
+        fdfk::TrackLevel& L = p.levels[l];
+        const uint64_t stride = l == 0 ? frame_stride_bytes : levels[l].frame_stride_bytes;
+        const uint64_t offset = l == 0 ? 0 : levels[l].offset_bytes;
+        L.prev = (l == 0 ? d_prev_frames : d_prev_pyramid) + offset + prev_first * stride;
+        L.next = (l == 0 ? d_next_frames : d_next_pyramid) + offset + next_first * stride;
+        L.prev_stride = L.next_stride = stride;
+        L.width = levels[l].width;
+        L.height = levels[l].height;
+    }
+    p.n_levels = n_levels;
+    p.n_frames = n_frames;
+    p.pts = d_points;
+    p.offs = d_offsets;
+    p.cap = cap;
+    p.keep = d_keep;
+    p.guess = reinterpret_cast<const int2*>(d_guess);
+    p.coords = coords;
+    p.radius = radius;
+    p.max_iters = max_iters;
+    p.eps = eps;
+    const uint32_t n = (2 * radius + 1) * (2 * radius + 1);
+    p.tau = ((double)min_eig * (double)n) * 1048576.0;
+    p.next_q11 = reinterpret_cast<int2*>(o.q11);
+    p.next_f32 = reinterpret_cast<float2*>(o.f32);
+    p.status = o.status;
+    p.err = o.err;
+    p.info = o.info;
+    p.matches = reinterpret_cast<uint2*>(o.matches);
+    // a wave per point and many iterations each: few points per workgroup
+    return fdfk::launch_track(p, chunks_per_frame(cap, n_frames, levels[0].width, levels[0].height,
+                                                  16, 1024), s);
+}
+
+inline bool aligned_to(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
+
+}  // namespace
+
+int fdf_track_device(fdf_ctx* ctx, const uint8_t* d_prev_frames, const uint8_t* d_prev_pyramid,
+                     uint32_t prev_first, const uint8_t* d_next_frames,
+                     const uint8_t* d_next_pyramid, uint32_t next_first, uint32_t n_frames,
+                     uint64_t frame_stride_bytes, const fdf_pyramid_level* levels,
+                     uint32_t n_levels, const void* d_points, uint32_t coords, uint64_t cap,
+                     const uint64_t* d_frame_offsets, const uint8_t* d_keep, const int32_t* d_guess,
+                     uint32_t radius, uint32_t max_iters, uint32_t eps, float min_eig,
+                     int32_t* d_next_q11, float* d_next_f32, uint8_t* d_status, uint32_t* d_err,
+                     uint32_t* d_info, fdf_match* d_matches, void* stream) {
+    if (!ctx) return FDF_ERR_ARG;
+    const int rc = check_track(n_frames, prev_first, next_first, frame_stride_bytes, levels,
+                               n_levels, coords, radius, max_iters, min_eig);
+    if (rc) return rc;
+    if (n_frames == 0) return FDF_OK;
+    if (!d_frame_offsets || !d_prev_frames || !d_next_frames ||
+        (n_levels > 1 && (!d_prev_pyramid || !d_next_pyramid)) ||
+        prev_first > 65535u || next_first > 65535u)
+        return FDF_ERR_ARG;
+    if (cap == 0) return FDF_OK;
+    if (!d_points || !d_next_q11 || !d_status || !aligned_to(d_points, 8) ||
+        !aligned_to(d_guess, 8) || !aligned_to(d_next_q11, 8) || !aligned_to(d_next_f32, 8) ||
+        !aligned_to(d_matches, 8) || !aligned_to(d_err, 4) || !aligned_to(d_info, 4) ||
+        (d_matches && cap > fdfk::kMatchMaxCap))
+        return FDF_ERR_ARG;
+    DeviceGuard guard(ctx->device);
+    const TrackOutputs o{d_next_q11, d_next_f32, d_status, d_err, d_info, d_matches};
+    return status_of(track_enqueue(d_prev_frames, d_prev_pyramid, prev_first, d_next_frames,
+                                   d_next_pyramid, next_first, n_frames, frame_stride_bytes, levels,
+                                   n_levels, d_points, coords, cap, d_frame_offsets, d_keep, d_guess,
+                                   radius, max_iters, eps, min_eig, o,
+                                   reinterpret_cast<hipStream_t>(stream)));
+}
+
+int fdf_track_frames(fdf_ctx* ctx, const uint8_t* prev, const uint8_t* next, uint32_t width,
+                     uint32_t height, size_t stride_bytes, const void* points, uint32_t coords,
+                     size_t n_points, const int32_t* guess, uint32_t n_levels, uint32_t num,
+                     uint32_t den, uint32_t radius, uint32_t max_iters, uint32_t eps, float min_eig,
+                     int32_t* out_q11, float* out_f32, uint8_t* out_status, uint32_t* out_err,
+                     uint32_t* out_info) {
+    if (!ctx) return FDF_ERR_ARG;
+    // the two frames are one batch of two: one plan, one pyramid build, frame 0 into frame 1
+    fdf_pyramid_level levels[fdfk::kTrackMaxLevels];
+    uint64_t pyr_bytes = 0, n_taps = 0;
+    if (n_levels == 0 || n_levels > fdfk::kTrackMaxLevels) return FDF_ERR_ARG;
+    if (n_levels == 1) num = 2, den = 1;                // one level needs no ratio
+    int rc = fdf_pyramid_plan(width, height, num, den, n_levels, 2, levels, &pyr_bytes, &n_taps);
+    if (rc) return rc;
+    const uint64_t frame_bytes = (uint64_t)width * height;
+    rc = check_track(1, 0, 1, frame_bytes, levels, n_levels, coords, radius, max_iters, min_eig);
+    if (rc) return rc;
+    if (stride_bytes < width || (n_points && (!prev || !next || !points || !out_q11 || !out_status)))
+        return FDF_ERR_ARG;
+    if (n_points == 0) return FDF_OK;
+    std::vector<uint32_t> taps((size_t)n_taps);         // an asynchronous copy's source
+    if (fdf_pyramid_taps(levels, n_levels, width, height, taps.data()) != FDF_OK) return FDF_ERR_SIZE;
+    Arena a(ctx);
+    const auto d_frames = a.part<uint8_t>(2 * frame_bytes);
+    const auto d_pyr = a.part<uint8_t>(pyr_bytes);
+    const auto d_taps = a.part<uint32_t>(taps.size());
+    const auto d_pts = a.part<uint64_t>(n_points);
+    const auto d_guess = a.part<uint64_t>(guess ? n_points : 0);
+    const auto d_offs = a.part<uint64_t>(2);
+    const auto d_q11 = a.part<uint64_t>(n_points);
+    const auto d_f32 = a.part<uint64_t>(out_f32 ? n_points : 0);
+    const auto d_status = a.part<uint8_t>(n_points);
+    const auto d_err = a.part<uint32_t>(out_err ? n_points : 0);
+    const auto d_info = a.part<uint32_t>(out_info ? n_points : 0);
+    if (a.open() != FDF_OK) return FDF_ERR_ALLOC;
+    if (a.ok())
+        a.note(upload_rows(a.at(d_frames), prev, stride_bytes, width, height, ctx->stream));
+    if (a.ok())
+        a.note(upload_rows(a.at(d_frames) + frame_bytes, next, stride_bytes, width, height,
+                           ctx->stream));
+    if (!taps.empty()) a.upload(d_taps, taps.data());
+    a.upload(d_pts, static_cast<const uint64_t*>(points));
+    if (guess) a.upload(d_guess, reinterpret_cast<const uint64_t*>(guess));
+    a.upload_one_frame(d_offs, n_points);
+    if (a.ok() && n_levels > 1 &&
+        fdf_pyramid_device(ctx, a.at(d_frames), 2, frame_bytes, levels, n_levels, a.at(d_pyr),
+                           a.at(d_taps), ctx->stream) != FDF_OK)
+        a.note(hipErrorInvalidValue);
+    if (a.ok()) {
+        const TrackOutputs o{reinterpret_cast<int32_t*>(a.at(d_q11)),
+                             out_f32 ? reinterpret_cast<float*>(a.at(d_f32)) : nullptr,
+                             a.at(d_status), out_err ? a.at(d_err) : nullptr,
+                             out_info ? a.at(d_info) : nullptr, nullptr};
+        a.note(track_enqueue(a.at(d_frames), a.at(d_pyr), 0, a.at(d_frames), a.at(d_pyr), 1, 1,
+                             frame_bytes, levels, n_levels, a.at(d_pts), coords, n_points,
+                             a.at(d_offs), nullptr,
+                             guess ? reinterpret_cast<const int32_t*>(a.at(d_guess)) : nullptr,
+                             radius, max_iters, eps, min_eig, o, ctx->stream));
+    }
+    a.download(reinterpret_cast<uint64_t*>(out_q11), d_q11, n_points);
+    if (out_f32) a.download(reinterpret_cast<uint64_t*>(out_f32), d_f32, n_points);
+    a.download(out_status, d_status, n_points);
+    if (out_err) a.download(out_err, d_err, n_points);
+    if (out_info) a.download(out_info, d_info, n_points);
+    return a.close();
 }
 
 // ---- brute-force Hamming matching (fdf_match.hip) ------------------------------------------

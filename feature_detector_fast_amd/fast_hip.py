@@ -1999,6 +1999,207 @@ def refine_model(q_points, t_points, matches, estimate, keep=None, model="homogr
     return (out["h"][0].reshape(3, 3).copy() if found else None), mask.astype(bool), out[0], rounds
 
 
+# Pyramidal Lucas-Kanade tracking (fdf_track.hip; include/fdf.h has the rule).
+
+TRACK_REASONS = ("skipped", "tracked", "eigenvalue", "left the frame", "step too large")
+TrackResult = collections.namedtuple("TrackResult", "q11 xy status err reason iterations")
+
+
+def _track_map(fn, name, v, a, b):
+    v, a, b = int(v), int(a), int(b)
+    if not (-(1 << 63) <= v < (1 << 63) and 0 <= a <= 0xffffffff and 0 <= b <= 0xffffffff):
+        raise ValueError("arguments must fit int64 and u32")
+    out = ctypes.c_int64()
+    check(fn(v, a, b, ctypes.byref(out)), name)
+    return out.value
+
+
+def track_map_position(x, len0, len_l):
+    """A level-0 position ``x`` in 1/2048 pixel on an axis of ``len0`` pixels at a level of
+    ``len_l`` pixels (fdf_track_map_position; host only, no device)."""
+    return _track_map(_native.load().fdf_track_map_position, "fdf_track_map_position", x, len0,
+                      len_l)
+
+
+def track_map_displacement(d, len_from, len_to):
+    """A displacement ``d`` in 1/2048 pixel carried from a level of ``len_from`` pixels to one of
+    ``len_to`` (fdf_track_map_displacement; host only, no device)."""
+    return _track_map(_native.load().fdf_track_map_displacement, "fdf_track_map_displacement", d,
+                      len_from, len_to)
+
+
+def _track_coords(coords):
+    try:
+        return {"u32": _native.FDF_COORDS_U32, "q11": _native.FDF_COORDS_Q11}[coords]
+    except (KeyError, TypeError):
+        raise ValueError('coords must be "u32" or "q11"') from None
+
+
+def _track_values(radius, max_iters, eps, min_eig):
+    radius, max_iters, eps, min_eig = int(radius), int(max_iters), int(eps), float(min_eig)
+    if not 1 <= radius <= 15:
+        raise ValueError("radius must be in 1..15")
+    if not 1 <= max_iters <= 64:
+        raise ValueError("max_iters must be in 1..64")
+    if not 0 <= eps <= 0xffffffff:
+        raise ValueError("eps must fit u32")
+    if not (min_eig >= 0.0 and np.isfinite(np.float32(min_eig))):
+        raise ValueError("min_eig must be finite and not negative")
+    return radius, max_iters, eps, min_eig
+
+
+def _track_set(torch, side, name):
+    """(frames, buffer or None, plan) of a Pyramid or of such a triple."""
+    if isinstance(side, Pyramid):
+        side = (side.frames, side.buffer, side.plan)
+    try:
+        frames, buffer, plan = side
+    except (TypeError, ValueError):
+        raise TypeError(f"{name} must be a Pyramid or (frames, buffer, plan)") from None
+    if not isinstance(plan, PyramidPlan):
+        raise TypeError(f"{name}: plan must be a PyramidPlan (pyramid_plan)")
+    _check_frames(torch, frames, name)
+    f, h, w = frames.shape
+    if (w, h) != (plan.levels[0].width, plan.levels[0].height):
+        raise ValueError(f"{name}: the frames do not have the plan's level-0 size")
+    if len(plan) > 1:
+        if f > plan.n_frames:
+            raise ValueError(f"{name}: more frames than the plan was made for")
+        if buffer is None or buffer.dtype != torch.uint8 or not buffer.is_contiguous() or \
+                buffer.numel() < plan.total_bytes:
+            raise ValueError(f"{name}: buffer must be a contiguous uint8 tensor of "
+                             "plan.total_bytes bytes")
+    else:
+        buffer = None
+    return frames, buffer, plan
+
+
+def track_device(prev, next, points, offsets, next_q11, status, prev_first=0, next_first=0,
+                 n_frames=None, coords="u32", keep=None, guess=None, radius=10, max_iters=30,
+                 eps=20, min_eig=1.0, next_xy=None, err=None, info=None, matches=None,
+                 stream=None, device=None):
+    """Pyramidal Lucas-Kanade tracking on the device (fdf_track_device): frame f of the call
+    follows its points from frame ``prev_first + f`` of ``prev`` into frame ``next_first + f`` of
+    ``next``.  ``prev`` and ``next`` are :class:`Pyramid` objects (built) or triples (frames,
+    buffer, plan) with equal plans and equal frame strides; they may be the same object: a batch
+    of F frames tracked frame to frame is ``track_device(p, p, ..., prev_first=0, next_first=1)``.
+    ``n_frames`` defaults to the frames both sides have from their first index on.
+
+    ``points`` (cap, 2) 32-bit integers: pixels (``coords="u32"``, as detect_device and
+    select_device fill them) or 1/2048 pixel (``coords="q11"``, as this call writes ``next_q11``);
+    ``offsets`` int64 with n_frames + 1 entries; ``keep`` (optional, (cap,) uint8) 0 skips a point;
+    ``guess`` (optional, (cap, 2) int32, 1/2048 pixel) is the starting position in the next frame.
+    ``radius`` 1..15 is the window's half side, ``max_iters`` 1..64 per level, ``eps`` the step in
+    1/2048 pixel at which a level stops, ``min_eig`` the smallest eigenvalue of the window's mean
+    gradient matrix a level must have.
+
+    Outputs, all (cap, ...) and contiguous: ``next_q11`` (cap, 2) int32 and ``status`` (cap,) uint8
+    always; ``next_xy`` (cap, 2) float32, ``err`` and ``info`` (cap,) 32-bit integers and
+    ``matches`` (cap, 2) 32-bit integers (match_device's records, for ransac_device) if given.
+    Asynchronous on ``stream`` (default: torch's current stream)."""
+    import torch
+
+    pf, pb, plan = _track_set(torch, prev, "prev")
+    nf, nb, nplan = _track_set(torch, next, "next")
+    if plan.levels != nplan.levels:
+        raise ValueError("prev and next must have the same levels (sizes, strides and offsets)")
+    prev_first, next_first = int(prev_first), int(next_first)
+    if prev_first < 0 or next_first < 0:
+        raise ValueError("first-frame indices must not be negative")
+    room = min(pf.shape[0] - prev_first, nf.shape[0] - next_first)
+    n = room if n_frames is None else int(n_frames)
+    if n < 0 or n > room:
+        raise ValueError("prev and next do not hold frames up to first + n_frames")
+    if n > 65535 or prev_first > 65535 or next_first > 65535:
+        raise ValueError("at most 65535 frames")
+    stride = max(pf.stride(0), nf.stride(0)) if max(pf.shape[0], nf.shape[0]) > 1 else \
+        pf.shape[1] * pf.shape[2]
+    for t in (pf, nf):
+        if t.shape[0] > 1 and t.stride(0) != stride:
+            raise ValueError("prev and next must have the same frame stride")
+    code = _track_coords(coords)
+    radius, max_iters, eps, min_eig = _track_values(radius, max_iters, eps, min_eig)
+    _check_points(points)
+    cap = points.shape[0]
+    _check_offsets(torch, offsets, n + 1)
+    tensors = [pf, nf, points, offsets, next_q11, status]
+    tensors += [t for t in (pb, nb, keep, guess, next_xy, err, info, matches) if t is not None]
+    for t, name in ((next_q11, "next_q11"), (guess, "guess"), (matches, "matches")):
+        if t is not None:
+            _check_points(t, name)
+    for t, name in ((next_q11, "next_q11"), (guess, "guess"), (matches, "matches"), (points, "points")):
+        if t is not None and (t.shape[0] < cap or t.data_ptr() % 8):
+            raise ValueError(f"{name} must hold cap rows and be 8-byte aligned")
+    if next_xy is not None and (next_xy.dtype != torch.float32 or next_xy.dim() != 2 or
+                                next_xy.shape[1] != 2 or next_xy.shape[0] < cap or
+                                not next_xy.is_contiguous() or next_xy.data_ptr() % 8):
+        raise ValueError("next_xy must be a contiguous, 8-byte aligned (cap, 2) float32 tensor")
+    for t, name in ((status, "status"), (keep, "keep")):
+        if t is not None and (t.dtype != torch.uint8 or t.dim() != 1 or t.numel() < cap or
+                              not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous uint8 tensor with cap entries")
+    for t, name in ((err, "err"), (info, "info")):
+        if t is not None and (t.dim() != 1 or t.element_size() != 4 or t.is_floating_point() or
+                              t.numel() < cap or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous 32-bit integer tensor with cap entries")
+    if matches is not None and cap > _MATCH_MAX_CAP:
+        raise ValueError("matches: cap is at most 2^32 - 2")
+    _check_one_device("track_device", tensors)
+    dev, stream = _device_stream(torch, pf, device, stream)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    rc = _native.load().fdf_track_device(
+        context(dev).handle, ptr(pf), ptr(pb), prev_first, ptr(nf), ptr(nb), next_first, n, stride,
+        plan._c, len(plan), ptr(points), code, cap, ptr(offsets), ptr(keep), ptr(guess), radius,
+        max_iters, eps, min_eig, ptr(next_q11), ptr(next_xy), ptr(status), ptr(err), ptr(info),
+        ptr(matches), ctypes.c_void_p(stream.cuda_stream))
+    check(rc, "fdf_track_device")
+
+
+def track_array(img0, img1, points, n_levels=3, scale=(2, 1), radius=10, max_iters=30, eps=20,
+                min_eig=1.0, guess=None, coords="u32", device=0):
+    """The ``points`` of host image ``img0`` followed into ``img1`` (same size) by pyramidal
+    Lucas-Kanade over ``n_levels`` levels at the factor ``scale`` (fdf_track_frames).  ``points``
+    is (K, 2) integers: pixels, or 1/2048 pixel with ``coords="q11"``; ``guess`` (optional, (K, 2),
+    1/2048 pixel) the starting positions in ``img1``.  Returns a :class:`TrackResult`: ``q11``
+    (K, 2) int32 positions in 1/2048 pixel ((-1, -1) for a lost point), ``xy`` (K, 2) float32
+    pixels, ``status`` (K,) bool, ``err`` (K,) uint32 (the window's sum of absolute differences in
+    1/32 grey level), ``reason`` (K,) uint8 (an index into TRACK_REASONS) and ``iterations``."""
+    a, b = _as_pixels(img0), _as_pixels(img1)
+    if a.shape != b.shape:
+        raise ValueError("img0 and img1 must have the same shape")
+    if a.strides[0] != b.strides[0]:
+        b = np.ascontiguousarray(b)
+        a = np.ascontiguousarray(a)
+    code = _track_coords(coords)
+    pts = np.asarray(points)
+    if pts.ndim != 2 or pts.shape[1] != 2 or pts.dtype.kind not in "ui":
+        raise TypeError("points must be a (K, 2) integer array")
+    pts = _host_points(pts) if code == _native.FDF_COORDS_U32 else \
+        np.ascontiguousarray(pts, dtype=np.int32)
+    k = len(pts)
+    g = None
+    if guess is not None:
+        g = np.ascontiguousarray(np.asarray(guess), dtype=np.int32)
+        if g.shape != (k, 2):
+            raise ValueError("guess must be (K, 2)")
+    num, den = _scale(scale)
+    radius, max_iters, eps, min_eig = _track_values(radius, max_iters, eps, min_eig)
+    h, w = a.shape
+    q11 = np.full((k, 2), -1, dtype=np.int32)
+    xy = np.full((k, 2), -1.0, dtype=np.float32)
+    status = np.zeros(k, dtype=np.uint8)
+    err = np.full(k, 0xffffffff, dtype=np.uint32)
+    info = np.zeros(k, dtype=np.uint32)
+    ptr = lambda t: t.ctypes.data if t is not None and t.size else None
+    rc = _native.load().fdf_track_frames(
+        context(device).handle, a.ctypes.data, b.ctypes.data, w, h, a.strides[0], ptr(pts), code, k,
+        ptr(g), int(n_levels), num, den, radius, max_iters, eps, min_eig, ptr(q11), ptr(xy),
+        ptr(status), ptr(err), ptr(info))
+    check(rc, "fdf_track_frames")
+    return TrackResult(q11, xy, status.astype(bool), err, (info & 0xff).astype(np.uint8),
+                       info >> 8)
+
+
 __all__ = ["NORTH", "EAST", "SOUTH", "WEST", "circle", "calculate_offsets", "context",
            "shard_contexts", "capacity_guess", "Lanes",
            "detect_array", "detector", "detector_batch", "detect_device", "keypoint_scores",
@@ -2017,6 +2218,8 @@ __all__ = ["NORTH", "EAST", "SOUTH", "WEST", "circle", "calculate_offsets", "con
            "unpack_models", "estimate_model",
            "refine_scratch_bytes", "refine_device", "refine_model",
            "warp_device", "warp_array", "model_invert",
+           "TRACK_REASONS", "TrackResult", "track_device", "track_array", "track_map_position",
+           "track_map_displacement",
            "detect_rgb_array", "detector_rgb", "rgb_to_luma", "detect_device_rgb",
            "score_rings", "score_rings_device", "keypoint_score_max_threshold",
            "keypoint_score_sum_abs_difference", "NonMaximalSuppression"]

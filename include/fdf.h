@@ -40,7 +40,9 @@ extern "C" {
  * fdf_pyramid_device, and fdf_harris_codes, fdf_harris_device and fdf_harris_points, and
  * fdf_ransac_sample, fdf_ransac_scratch_bytes, fdf_ransac_device and fdf_ransac_points, and
  * fdf_refine_scratch_bytes, fdf_refine_device and fdf_refine_points, and fdf_warp_device,
- * fdf_warp_frame and fdf_model_invert. */
+ * fdf_warp_frame and fdf_model_invert, and fdf_track_device, fdf_track_frames,
+ * fdf_track_map_position and fdf_track_map_displacement (with FDF_COORDS_Q11, which only the
+ * tracker accepts). */
 #define FDF_ABI_VERSION 6
 
 /* Status codes.  Shapes the reference maps to an empty Vec return FDF_OK with 0 points. */
@@ -750,6 +752,7 @@ int fdf_match_points(fdf_ctx* ctx, const uint8_t* q_desc, const fdf_point* q_poi
  */
 #define FDF_COORDS_U32 0u   /* fdf_point */
 #define FDF_COORDS_F32 1u   /* float x, y */
+#define FDF_COORDS_Q11 2u   /* int32 x, y in 1/2048 pixel: fdf_track_device only (rejected here) */
 #define FDF_MODEL_AFFINE 0u
 #define FDF_MODEL_HOMOGRAPHY 1u
 #define FDF_RANSAC_NONE 0xFFFFFFFFu   /* hypothesis of a frame without a model; an idx of no sample */
@@ -1049,6 +1052,154 @@ int fdf_warp_frame(fdf_ctx* ctx, const uint8_t* data, uint32_t width, uint32_t h
                    uint32_t dst_h, size_t out_stride_bytes, uint32_t border, uint32_t fill,
                    uint8_t* out_mask);
 int fdf_model_invert(const double h[9], double out[9]);
+
+/*
+ * Pyramidal Lucas-Kanade tracking of keypoints from one frame into another (extension: the
+ * FAST + KLT front end, OpenCV's calcOpticalFlowPyrLK, with an integer contract).  Corners are
+ * detected once and then followed from frame to frame at sub-pixel precision, without
+ * descriptors.  Positions are held in 1/2048 pixel -- "Q11" below is an int32 in that unit -- so
+ * every sum of an iteration is an integer sum, exact in any order, and only a 2 x 2 solve is
+ * floating point: a short fixed sequence of unfused binary64 operations.  A numpy restatement
+ * reproduces every output bit for bit.  These are not OpenCV's bits.
+ *
+ * Frames and levels.  `levels` is a host array of n_levels (1..32) fdf_pyramid_level entries, as
+ * fdf_pyramid_device takes them.  Level 0 is the caller's frames, frame_stride_bytes apart;
+ * levels >= 1 live in a pyramid buffer.  The previous and the next set each have a frames
+ * pointer, a pyramid pointer and a first-frame index: frame f of the call (f < n_frames) reads
+ * previous frame prev_first + f and next frame next_first + f, where
+ *   level 0 of frame k is at d_frames + k * frame_stride_bytes,
+ *   level l >= 1 of frame k at d_pyramid + levels[l].offset_bytes + k * levels[l].frame_stride_bytes.
+ * Tracking every frame of a batch of F into the next one passes the same frames and pyramid
+ * twice with prev_first = 0, next_first = 1, n_frames = F - 1 (a pointer shift cannot say this:
+ * the levels have different strides).  The caller guarantees that both sets hold frames up to
+ * first + n_frames.  With n_levels == 1 the pyramid pointers may be NULL.  Any ratio between the
+ * levels is legal; 2 : 1 is the usual choice for tracking.
+ *
+ * Points.  Indexing as in fdf_orient_device: frame f owns [offs[f], min(offs[f+1], cap)).
+ * `coords` is FDF_COORDS_U32 (an fdf_point, X0 = 2048 x) or FDF_COORDS_Q11 (two int32, x then y,
+ * as this stage writes them, so that a caller chains f -> f+1 -> f+2 at sub-pixel positions).
+ * Optional d_keep (cap bytes): 0 skips the point.  Optional d_guess (cap x two int32, Q11): the
+ * starting position in the next frame at level 0; NULL means the point's own position.  A point
+ * is skipped if its keep byte is 0 or if its position or its guess lies outside
+ * [0, (w0 - 1) * 2048] x [0, (h0 - 1) * 2048]; it gets reason 0 and the lost outputs below, and no
+ * frame byte is read for it.
+ *
+ * Sample.  For a frame of W x H and a Q11 position (X, Y): ix = X >> 11, qx = X & 2047 (the same
+ * for y), w_0 = 2048 - q, w_1 = q, and
+ *   S(X, Y) = (sum over a, b in {0, 1} of wy_b * wx_a *
+ *              I(clamp(ix + a, 0, W - 1), clamp(iy + b, 0, H - 1)) + 2^16) >> 17,
+ * the resize's sum rounded once to 5 fractional bits: 0..8160.
+ *
+ * Level maps (int64, `/` is floor division), also exported as host-only functions:
+ *   map_pos(X, len0, lenl)  = clamp(((X + 1024) * lenl * 2 + len0) / (2 * len0) - 1024,
+ *                                   0, (lenl - 1) * 2048)       level 0 directly to level l
+ *   map_disp(D, from, to)   = (2 * D * to + from) / (2 * from)  the floor for negative D too
+ * map_pos(29372, 32, 16) = 14174, map_disp(-3001, 16, 32) = -6002, map_disp(-3001, 32, 16) =
+ * -1500, map_disp(5, 6, 5) = 4.  fdf_track_map_position / fdf_track_map_displacement: lengths
+ * 1..65535 and |v| <= 2^28 (so 2 v len stays within int64), a non-NULL `out`; else FDF_ERR_ARG.
+ *
+ * Per point.  r = radius (1..15), n = (2 r + 1)^2, tau = ((double)min_eig * (double)n) * 1048576.0
+ * (min_eig, a finite float >= 0: the smallest eigenvalue of the window's mean gradient matrix a
+ * level must have, in grey levels^2 per pixel^2; 1048576 = (32 * 32)^2, the sample's and the
+ * Scharr weights' gain squared).  The displacement starts at the coarsest level as
+ * D = map_disp(guess - X0, len0, len_{L-1}) per axis, 0 without a guess.  Levels are visited from
+ * l = L - 1 down to 0; before every level but the first, D = map_disp(D, len_{l+1}, len_l) per
+ * axis.  At each level:
+ *   1. Template.  (Xp, Yp) = map_pos of the level-0 position.  P(i, j) = S_prev(Xp + 2048 i,
+ *      Yp + 2048 j) for |i|, |j| <= r + 1: one pair of fractional weights serves the whole patch.
+ *      Scharr gradients for |i|, |j| <= r:
+ *        Gx(i, j) = 3 (P(i+1, j-1) - P(i-1, j-1)) + 10 (P(i+1, j) - P(i-1, j))
+ *                 + 3 (P(i+1, j+1) - P(i-1, j+1)),  Gy the transpose of that;  |G| <= 130560.
+ *      A11 = sum Gx^2, A12 = sum Gx Gy, A22 = sum Gy^2 in int64: below 2^44, exact as the doubles
+ *      a11, a12, a22.
+ *   2. Usable level.  p = a11 - tau, q = a22 - tau; the level is usable iff p + q > 0 and
+ *      p * q - a12 * a12 > 0 (each step one binary64 operation; both eigenvalues of A exceed tau,
+ *      without a square root).  A level >= 1 that is not usable is skipped with D unchanged; if
+ *      level 0 is not usable the point is lost with reason 2.  det = a11 * a22 - a12 * a12 is > 0
+ *      whenever the test passes: then p, q > 0, so a11 >= p and a22 >= q, rounded products and
+ *      differences are monotone, and det >= p * q - a12 * a12 > 0.
+ *   3. Start.  (Xn, Yn) = (Xp, Yp) + D; outside [0, (W_l - 1) * 2048] x [0, (H_l - 1) * 2048] the
+ *      point is lost with reason 3.
+ *   4. Iterate, at most max_iters (1..64) times per level:
+ *        J(i, j) = S_next(Xn + 2048 i, Yn + 2048 j), E = J - P, |i|, |j| <= r;
+ *        b1 = sum E Gx, b2 = sum E Gy in int64 (|b| < 2^41, exact as doubles);
+ *        dx = (a12 * b2 - a22 * b1) / det,  dy = (a12 * b1 - a11 * b2) / det;
+ *        FDX = floor(dx * 65536.0 + 0.5), FDY the same (65536 = 32, the sample's fractional
+ *        bits, * 2048; the Scharr gain cancels);
+ *        unless |FDX| <= 2^20 and |FDY| <= 2^20 (false for a NaN) the point is lost, reason 4;
+ *        Xn += FDX, Yn += FDY; outside the level the point is lost with reason 3;
+ *        the level stops once |FDX| + |FDY| <= eps after the update (eps: Q11 units, 20 is about
+ *        0.01 pixel).  A level that uses all its iterations is not an error.
+ *      An iteration counts once its b1 and b2 are summed, whatever follows.
+ *   5. Carry.  D = (Xn, Yn) - (Xp, Yp).
+ * After level 0 the point is tracked with reason 1 and err = sum |S_next(Xn + 2048 i, Yn + 2048 j)
+ * - P(i, j)| over the window at the final position (one more sampling pass, <= 961 * 8160).
+ *
+ * Outputs.  Entries at index >= min(offs[n_frames], cap) are never written.  All but d_next_q11
+ * and d_status are optional.
+ *   output                          tracked point                    lost or skipped point
+ *   d_next_q11 (2 x int32)          (Xn, Yn)                         (-1, -1): an invalid input,
+ *                                                                    a chained call skips it
+ *   d_next_f32 (2 x float, the      (float)((double)Xn / 2048.0),    -1.0f, -1.0f
+ *     layout of FDF_COORDS_F32)     the same for y
+ *   d_status (u8)                   1                                0
+ *   d_err (u32)                     err                              0xFFFFFFFF
+ *   d_info (u32)                    reason | iterations << 8, the iterations summed over all levels
+ *   d_matches (fdf_match)           {i, min(err / n, 0xFFFE), 0xFFFF} {FDF_MATCH_NONE, 0xFFFF, 0xFFFF}
+ * Reasons: 0 skipped, 1 tracked, 2 level-0 eigenvalue test, 3 left the frame, 4 step too large.
+ *
+ * Into the estimator.  d_matches, the point offsets as both query and train offsets, d_status as
+ * d_keep and d_next_f32 as the FDF_COORDS_F32 train coordinates go into fdf_ransac_device as they
+ * are; the query side then needs an FDF_COORDS_F32 copy of the points (one format serves both
+ * sides of that call).  With FDF_COORDS_U32 points on both sides instead, a second array of
+ * rounded next positions is the caller's to make.
+ *
+ * Example.  32 x 24 frames, A(x, y) = min(255, ((x-16)^2 + 2 (y-12)^2 + (x-16)(y-12)) >> 2) and
+ * B(x, y) = A(clamp(x - 2), clamp(y - 1)); the point (14, 10), r = 3, max_iters 30, eps 20,
+ * min_eig 0.25, one level: A11 = 184786944, A12 = 270729216, A22 = 533045248, the first
+ * b = (-24637440, -41500672), the position after one iteration (33605, 23077) (with max_iters = 1
+ * the result, err 1789); the full run ends at (32773, 22529), err 0, 4 iterations.  min_eig = 1.0:
+ * lost, reason 2.  Two levels 2 : 1 (16 x 12): (32773, 22530), err 0, 5 iterations.  The Q11
+ * start (29372, 21780): one level (33469, 23826), err 0; two levels (33468, 23826), err 2.  A
+ * constant frame is lost with reason 2 even at min_eig = 0.
+ *
+ * fdf_track_device: asynchronous on `stream` (NULL = the HIP null stream); like fdf_orient_device
+ * it takes no context lock, uses no workspace and allocates nothing; it only binds the context's
+ * device.  Whatever the points, keep bytes and guesses hold, no access leaves the frames' bytes
+ * or the other buffers: taps are clamped, positions are checked before use and frames are read
+ * through buffer resources of exactly a level's bytes.  FDF_ERR_ARG, synchronously and with
+ * nothing launched: radius outside 1..15, max_iters outside 1..64, a negative or non-finite
+ * min_eig, a bad `coords`, n_frames > 65535 or a first-frame index above 65535, n_levels outside
+ * 1..32, a NULL required pointer or a NULL pyramid with n_levels > 1, misaligned arrays
+ * (coordinates, guesses and matches 8 bytes; err and info 4 bytes), d_matches with cap above
+ * 2^32 - 2, a frame stride (of any level) below width * height when more than one frame is
+ * addressed.  FDF_ERR_SIZE: a zero level dimension, a side above 65535, width * height above
+ * 2^31 - 256.  n_frames == 0: FDF_OK, nothing written.
+ *
+ * fdf_track_frames: two host frames of one size (rows stride_bytes apart) and n_points host
+ * points (`coords` as above; `guess` optional).  Builds both pyramids for num / den and n_levels
+ * with fdf_pyramid_plan, fdf_pyramid_taps and the resize kernel (num and den are not looked at
+ * when n_levels == 1), then tracks; synchronous.  Its buffers are allocated and freed by the
+ * call; the context's workspace and retained result are untouched, so fdf_fetch_last stays
+ * valid.  out_q11 and out_status are required, the others optional.
+ */
+int fdf_track_map_position(int64_t x, uint32_t len0, uint32_t len_l, int64_t* out);
+int fdf_track_map_displacement(int64_t d, uint32_t len_from, uint32_t len_to, int64_t* out);
+int fdf_track_device(fdf_ctx* ctx, const uint8_t* d_prev_frames, const uint8_t* d_prev_pyramid,
+                     uint32_t prev_first, const uint8_t* d_next_frames,
+                     const uint8_t* d_next_pyramid, uint32_t next_first, uint32_t n_frames,
+                     uint64_t frame_stride_bytes, const fdf_pyramid_level* levels,
+                     uint32_t n_levels, const void* d_points, uint32_t coords, uint64_t cap,
+                     const uint64_t* d_frame_offsets, const uint8_t* d_keep, const int32_t* d_guess,
+                     uint32_t radius, uint32_t max_iters, uint32_t eps, float min_eig,
+                     int32_t* d_next_q11, float* d_next_f32, uint8_t* d_status, uint32_t* d_err,
+                     uint32_t* d_info, fdf_match* d_matches, void* stream);
+int fdf_track_frames(fdf_ctx* ctx, const uint8_t* prev, const uint8_t* next, uint32_t width,
+                     uint32_t height, size_t stride_bytes, const void* points, uint32_t coords,
+                     size_t n_points, const int32_t* guess, uint32_t n_levels, uint32_t num,
+                     uint32_t den, uint32_t radius, uint32_t max_iters, uint32_t eps, float min_eig,
+                     int32_t* out_q11, float* out_f32, uint8_t* out_status, uint32_t* out_err,
+                     uint32_t* out_info);
 
 /*
  * Streaming host pipeline (extension; the reference's callers detect on one

@@ -23,6 +23,7 @@
 //   (none: ... and refine it)        --                   fdf::refine_model(q_points, t_points, matches, estimate, ...)
 //   (none: ... over a scale pyramid) --                   fdf::resize, fdf::pyramid_plan, fdf::build_pyramid
 //   (none: ... and warp by the model) --                  fdf::warp, fdf::model_invert
+//   (none: ... or track the points)  --                   fdf::track
 //
 // Where the reference panics (n < 9, n > 16, degenerate sizes) these throw fdf::Error.
 // Each thread lazily owns one device context per HIP device (device 0 unless
@@ -496,6 +497,45 @@ inline std::array<double, 9> model_invert(const double (&h)[9]) {
     std::array<double, 9> out{};
     check(fdf_model_invert(h, out.data()), "fdf_model_invert");
     return out;
+}
+
+// Pyramidal Lucas-Kanade tracking of `points` (pixels) of `prev` into `next`, two frames of one
+// size (extension, fdf_track_frames; include/fdf.h has the rule).  Entry k of every array belongs
+// to point k: q11 is the position in 1/2048 pixel ((-1, -1) for a lost point), xy the same in
+// pixels, info = reason | iterations << 8 (reason 1 = tracked).
+struct TrackOptions {
+    uint32_t n_levels = 3, num = 2, den = 1;   // the pyramid: levels and the factor between them
+    uint32_t radius = 10, max_iters = 30, eps = 20;
+    float min_eig = 1.0f;
+};
+struct Tracks {
+    std::vector<std::array<int32_t, 2>> q11;
+    std::vector<std::array<float, 2>> xy;
+    std::vector<uint8_t> status;
+    std::vector<uint32_t> err, info;
+};
+inline Tracks track(const GrayView& prev, const GrayView& next, const std::vector<Point>& points,
+                    const TrackOptions& opt, Context& ctx) {
+    if (prev.width != next.width || prev.height != next.height || prev.stride != next.stride)
+        throw Error(FDF_ERR_ARG, "fdf::track: the frames differ in size or stride");
+    const size_t n = points.size();
+    Tracks t;
+    t.q11.assign(n, {-1, -1});
+    t.xy.assign(n, {-1.0f, -1.0f});
+    t.status.assign(n, 0);
+    t.err.assign(n, 0xFFFFFFFFu);
+    t.info.assign(n, 0);
+    check(fdf_track_frames(ctx.get(), prev.data, next.data, prev.width, prev.height, prev.stride,
+                           points.data(), FDF_COORDS_U32, n, nullptr, opt.n_levels, opt.num,
+                           opt.den, opt.radius, opt.max_iters, opt.eps, opt.min_eig,
+                           n ? t.q11[0].data() : nullptr, n ? t.xy[0].data() : nullptr,
+                           t.status.data(), t.err.data(), t.info.data()),
+          "fdf_track_frames");
+    return t;
+}
+inline Tracks track(const GrayView& prev, const GrayView& next, const std::vector<Point>& points,
+                    const TrackOptions& opt = TrackOptions()) {
+    return track(prev, next, points, opt, thread_context());
 }
 
 inline std::vector<Point> detect(const GrayView& img, const Config& config) {
