@@ -7,7 +7,7 @@
 #                          fdf::keypoint_descriptors,
 #                          fdf::match_descriptors, fdf::resize / fdf::build_pyramid,
 #                          fdf::estimate_model, fdf::refine_model, fdf::warp,
-#                          fdf::track
+#                          fdf::track, fdf::update_tracks
 #   tests/cpp/test_wg_share  host-only check of the kernels' work split (fdf_common.h)
 #   tests/cpp/test_geometry  host-only table of the band geometry and launch plan (fdf_geometry.h)
 HIPCC ?= /opt/rocm/bin/hipcc
@@ -20,9 +20,9 @@ CSRC := $(PKG)/csrc
 LIBFDF := $(PKG)/libfdf.so
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Iinclude $(EXTRA_HIPFLAGS)
 OBJS := $(addprefix $(CSRC)/fdf_,$(addsuffix .o,kernels sweep sweep_latency sweep_rgb select \
-	orient harris describe match ransac resize warp track api stages pipeline))
+	orient harris describe match ransac resize warp track tracks api stages pipeline))
 HEADERS := $(wildcard $(CSRC)/*.h) include/fdf.h
-CPP_TESTS := $(addprefix tests/cpp/test_cpp_,api select orient harris describe match pyramid ransac refine warp track)
+CPP_TESTS := $(addprefix tests/cpp/test_cpp_,api select orient harris describe match pyramid ransac refine warp track tracks)
 
 all: $(LIBFDF) oracle/liboracle.so oracle/libfast_avx2.so $(CPP_TESTS) tests/cpp/test_wg_share \
 	tests/cpp/test_geometry

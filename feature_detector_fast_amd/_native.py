@@ -50,7 +50,8 @@ EXPORTED_SYMBOLS = (
     "fdf_ransac_scratch_bytes", "fdf_ransac_device", "fdf_ransac_points",
     "fdf_refine_scratch_bytes", "fdf_refine_device", "fdf_refine_points", "fdf_warp_device",
     "fdf_warp_frame", "fdf_model_invert", "fdf_track_device", "fdf_track_frames",
-    "fdf_track_map_position", "fdf_track_map_displacement",
+    "fdf_track_map_position", "fdf_track_map_displacement", "fdf_tracks_scratch_bytes",
+    "fdf_tracks_update_device", "fdf_tracks_update_points",
 )
 
 
@@ -82,11 +83,19 @@ class FdfModel(ctypes.Structure):
                 ("n_valid", ctypes.c_uint32)]
 
 
+class FdfTracksParams(ctypes.Structure):
+    """include/fdf.h fdf_tracks_params: 24 bytes."""
+    _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32),
+                ("min_dist", ctypes.c_uint32), ("margin", ctypes.c_uint32),
+                ("max_tracks", ctypes.c_uint32), ("passes", ctypes.c_uint32)]
+
+
 FDF_MATCH_NONE = 0xFFFFFFFF
 FDF_MATCH_NO_DISTANCE = 0xFFFF
 FDF_COORDS_U32 = 0
 FDF_COORDS_F32 = 1
 FDF_COORDS_Q11 = 2
+FDF_TRACKS_NEW = 0x80000000
 FDF_MODEL_AFFINE = 0
 FDF_MODEL_HOMOGRAPHY = 1
 FDF_RANSAC_NONE = 0xFFFFFFFF
@@ -311,6 +320,16 @@ def load():
     lib.fdf_track_frames.restype = ctypes.c_int
     lib.fdf_track_frames.argtypes = [vp, vp, vp, u32, u32, sz, vp, u32, sz, vp, u32, u32, u32, u32,
                                      u32, u32, ctypes.c_float, vp, vp, vp, vp, vp]
+    lib.fdf_tracks_scratch_bytes.restype = ctypes.c_int
+    lib.fdf_tracks_scratch_bytes.argtypes = [u32, u32, u32, u32, u64, u64, ctypes.POINTER(u64)]
+    lib.fdf_tracks_update_device.restype = ctypes.c_int
+    lib.fdf_tracks_update_device.argtypes = [vp, u32, ctypes.POINTER(FdfTracksParams), vp, vp, vp, vp,
+                                             vp, u64, vp, vp, vp, u64, vp, vp, vp, vp, vp, u64, vp,
+                                             vp, u64, vp]
+    lib.fdf_tracks_update_points.restype = ctypes.c_int
+    lib.fdf_tracks_update_points.argtypes = [vp, ctypes.POINTER(FdfTracksParams), vp, vp, vp, vp, sz,
+                                             vp, vp, sz, ctypes.POINTER(u32), vp, vp, vp, vp, sz,
+                                             ctypes.POINTER(sz)]
     del u8p
     _lib = lib
     return lib

@@ -1,6 +1,7 @@
 // fdf_common.h -- device helpers of every kernel file: a frame's index range, a workgroup's
-// share of it, raw buffer resources and the DPP sum of a keypoint's lanes (fdf_select.hip,
-// fdf_orient.hip, fdf_describe.hip, fdf_harris.hip);
+// share of it, the cut of a 256-bin histogram (fdf_select.hip, fdf_tracks.hip), raw buffer
+// resources and the DPP sum of a keypoint's lanes (fdf_select.hip, fdf_orient.hip,
+// fdf_describe.hip, fdf_harris.hip);
 // circle geometry, byte-SWAR comparisons, wave ballots, the per-lane segment test and the two
 // NMS score functions of the reference (fdf_sweep.hip, fdf_kernels.hip).
 #pragma once
@@ -30,6 +31,41 @@ __host__ __device__ inline IndexRange wg_share(uint64_t b, uint64_t e, uint32_t 
     per = (per + per_pass - 1) / per_pass * per_pass;
     const uint64_t lo = b + chunk * per < e ? b + chunk * per : e;
     return {lo, lo + per < e ? lo + per : e};
+}
+
+// Wave-wide: in the 256-bin histogram `h`, the highest-first position of the kk-th entry
+// (kk >= 1).  Lane l owns the bins 255 - 4l .. 252 - 4l.  Returns the total; when total >= kk
+// exactly one lane has `found` set with the bin and how many entries of that bin are needed.
+__device__ __forceinline__ uint32_t find_cut(const uint32_t* h, uint32_t kk, uint32_t lane,
+                                             bool& found, uint32_t& bin, uint32_t& need) {
+    uint32_t v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = h[255u - (4u * lane + j)];
+    const uint32_t s = v[0] + v[1] + v[2] + v[3];
+    uint32_t incl = s;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t o = __shfl_up(incl, d, 64);
+        if (lane >= (uint32_t)d) incl += o;
+    }
+    const uint32_t total = __shfl(incl, 63, 64);
+    uint32_t cum = incl - s;
+    found = cum < kk && kk <= incl;
+    bin = 0;
+    need = 0;
+    if (found) {
+        bool done = false;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (!done && cum + v[j] >= kk) {
+                bin = 255u - (4u * lane + j);
+                need = kk - cum;
+                done = true;
+            }
+            if (!done) cum += v[j];
+        }
+    }
+    return total;
 }
 
 // Word 3 of a raw buffer resource on gfx9: DATA_FORMAT = 32 (bits 15-18 = 4), no swizzle, no

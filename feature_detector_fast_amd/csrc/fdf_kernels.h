@@ -460,6 +460,56 @@ struct TrackParams {
 // one kernel on `stream`: `chunks` workgroups per frame share the frame's points
 hipError_t launch_track(const TrackParams& p, uint32_t chunks, hipStream_t stream);
 
+// Track-set maintenance between two tracking calls (fdf_tracks.hip; fdf_tracks_update_device):
+// prune, min-distance suppression by passes, refill from the candidates, ids and ages.
+constexpr int kTracksThreads = 256;
+constexpr int kTracksWaves = kTracksThreads / 64;
+constexpr uint32_t kTracksMinCell = 8;                // cell side = max(min_dist, kTracksMinCell)
+constexpr uint32_t kTracksMaxDist = 255;
+constexpr uint32_t kTracksMaxPasses = 32;
+constexpr uint32_t kTracksMaxSide = 65535;            // a pixel coordinate is a u16
+constexpr uint64_t kTracksMaxCap = 0xffffffffull;     // an entry holds its index as a u32
+constexpr uint32_t kTracksNewBit = 0x80000000u;       // d_out_src of a new track
+constexpr uint8_t kTracksUndecided = 0, kTracksAdmitted = 1, kTracksRejected = 2;
+
+// One list (tracks or candidates) of a call.  `ent`, `st[0..1]` are cell-sorted: stream f's
+// binned points are [lo, lo + start[f * (cells + 1) + cells]) with lo the stream's first index;
+// `flag` is by original index.
+struct TracksList {
+    const uint64_t* offs;        // n_frames + 1 entries
+    uint64_t cap;
+    uint32_t* cursor;            // n_frames * cells, zero before the count
+    uint32_t* start;             // n_frames * (cells + 1): a cell's first entry, relative to lo
+    uint4* ent;                  // cap entries {x | y << 16, priority key, original index, cell}
+    uint8_t* st[2];              // cap states each, read and written alternately
+    uint8_t* flag;               // cap: 1 = in the output, zero before the call's kernels
+    uint32_t chunks;             // workgroups per stream of the kernels that walk the list
+};
+struct TracksParams {
+    uint32_t n_frames, width, height, min_dist, margin, max_tracks, passes;
+    uint32_t cell, cells_x, cells_y;
+    const int2* t_q11;
+    const uint8_t* t_status;     // or NULL
+    const uint32_t* t_ids;
+    const uint32_t* t_ages;
+    const uint2* c_pts;
+    const uint16_t* c_scores;
+    TracksList t, c;
+    uint32_t* next_id;           // n_frames, in and out
+    uint32_t* kept;              // n_frames each: kept survivors, new tracks, the ids' base
+    uint32_t* n_new;
+    uint32_t* id_base;
+    uint64_t* tot;               // n_frames: kept + new
+    int2* out_q11;
+    uint32_t* out_ids;
+    uint32_t* out_ages;
+    uint32_t* out_src;           // or NULL
+    uint64_t out_cap;
+    uint64_t* out_offs;          // n_frames + 1
+};
+// all kernels of one update on `stream` (the cursors and flags are zeroed by the caller)
+hipError_t launch_tracks_update(const TracksParams& p, hipStream_t stream);
+
 // Brute-force Hamming matching of the 256-bit descriptors (fdf_match.hip; fdf_match_device,
 // fdf_match_filter_device).
 constexpr int kMatchThreads = 256;                    // queries of a workgroup pass

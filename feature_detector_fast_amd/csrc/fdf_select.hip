@@ -62,41 +62,6 @@ __device__ __forceinline__ uint64_t lower_bound_y(const uint2* pts, uint64_t b, 
     return b;
 }
 
-// Wave-wide: in the 256-bin histogram `h`, the highest-first position of the kk-th entry
-// (kk >= 1).  Lane l owns the bins 255 - 4l .. 252 - 4l.  Returns the total; when total >= kk
-// exactly one lane has `found` set with the bin and how many entries of that bin are needed.
-__device__ __forceinline__ uint32_t find_cut(const uint32_t* h, uint32_t kk, uint32_t lane,
-                                             bool& found, uint32_t& bin, uint32_t& need) {
-    uint32_t v[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = h[255u - (4u * lane + j)];
-    const uint32_t s = v[0] + v[1] + v[2] + v[3];
-    uint32_t incl = s;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(incl, d, 64);
-        if (lane >= (uint32_t)d) incl += o;
-    }
-    const uint32_t total = __shfl(incl, 63, 64);
-    uint32_t cum = incl - s;
-    found = cum < kk && kk <= incl;
-    bin = 0;
-    need = 0;
-    if (found) {
-        bool done = false;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (!done && cum + v[j] >= kk) {
-                bin = 255u - (4u * lane + j);
-                need = kk - cum;
-                done = true;
-            }
-            if (!done) cum += v[j];
-        }
-    }
-    return total;
-}
-
 __global__ __launch_bounds__(kSelThreads) void select_kernel(SelectParams P) {
     __shared__ uint32_t hist[kSelCells * 256];
     __shared__ uint32_t s_cut[kSelCells];            // pass 1: high byte; pass 2 on: s*

@@ -1,7 +1,7 @@
 // fdf_stages.cpp -- the C ABI of the stages behind the detector (extensions: the reference
 // returns points only): best-K selection, orientation, Harris response, steered BRIEF descriptors, box
 // smoothing, descriptor matching, RANSAC model estimation, the resize behind the scale pyramid, the warp by the estimated
-// models and Lucas-Kanade tracking.  Each has an asynchronous _device entry on the caller's stream and memory and a
+// models, Lucas-Kanade tracking and the track-set maintenance between two tracking calls.  Each has an asynchronous _device entry on the caller's stream and memory and a
 // host convenience _points entry.  Of a context they use the device, the mutex and the
 // stream only: its workspace and retained result (fdf_fetch_last) are not touched.
 #include <algorithm>
@@ -1153,6 +1153,236 @@ int fdf_track_frames(fdf_ctx* ctx, const uint8_t* prev, const uint8_t* next, uin
     if (out_err) a.download(out_err, d_err, n_points);
     if (out_info) a.download(out_info, d_info, n_points);
     return a.close();
+}
+
+// ---- track-set maintenance (fdf_tracks.hip) -----------------------------------------------
+namespace {
+
+static_assert(FDF_TRACKS_NEW == fdfk::kTracksNewBit, "the kernel's constant is the header's");
+
+// Scratch of one fdf_tracks_update_device call, every part 256-byte aligned.  Per list (tracks,
+// then candidates): the cells' cursors and the admitted flags (both zeroed on the stream before
+// the kernels), the cells' starts, the sorted entries and the two state buffers; then four
+// per-stream words and the per-stream totals.
+struct TracksListLayout {
+    uint64_t cursor = 0, start = 0, ent = 0, st0 = 0, st1 = 0, flag = 0;
+};
+struct TracksLayout {
+    uint32_t cell = 0, cells_x = 0, cells_y = 0;
+    TracksListLayout t, c;
+    uint64_t kept = 0, n_new = 0, id_base = 0, tot = 0, total = 0;
+};
+
+int tracks_layout(uint32_t n_frames, uint32_t width, uint32_t height, uint32_t min_dist,
+                  uint64_t t_cap, uint64_t c_cap, TracksLayout* L) {
+    if (width == 0 || height == 0 || width > fdfk::kTracksMaxSide ||
+        height > fdfk::kTracksMaxSide || min_dist == 0 || min_dist > fdfk::kTracksMaxDist ||
+        n_frames > 65535u || t_cap > fdfk::kTracksMaxCap || c_cap > fdfk::kTracksMaxCap)
+        return FDF_ERR_ARG;
+    L->cell = std::max(min_dist, fdfk::kTracksMinCell);
+    L->cells_x = (width + L->cell - 1) / L->cell;
+    L->cells_y = (height + L->cell - 1) / L->cell;
+    const uint64_t cells = (uint64_t)L->cells_x * L->cells_y;
+    uint64_t at = 0;
+    auto take = [&at](uint64_t bytes) {
+        const uint64_t o = at;
+        at += align256(bytes);
+        return o;
+    };
+    const uint64_t caps[2] = {t_cap, c_cap};
+    TracksListLayout* lists[2] = {&L->t, &L->c};
+    for (int k = 0; k < 2; ++k) {
+        lists[k]->cursor = take(sizeof(uint32_t) * cells * n_frames);
+        lists[k]->start = take(sizeof(uint32_t) * (cells + 1) * n_frames);
+        lists[k]->ent = take(16 * caps[k]);
+        lists[k]->st0 = take(caps[k]);
+        lists[k]->st1 = take(caps[k]);
+        lists[k]->flag = take(caps[k]);
+    }
+    L->kept = take(sizeof(uint32_t) * n_frames);
+    L->n_new = take(sizeof(uint32_t) * n_frames);
+    L->id_base = take(sizeof(uint32_t) * n_frames);
+    L->tot = take(sizeof(uint64_t) * n_frames);
+    L->total = at;
+    return FDF_OK;
+}
+
+inline bool tracks_values_ok(const fdf_tracks_params* p) {
+    return p && p->max_tracks >= 1 && p->passes >= 1 && p->passes <= fdfk::kTracksMaxPasses &&
+           p->width != 0 && p->height != 0 &&
+           2ull * p->margin < std::min(p->width, p->height);
+}
+
+}  // namespace
+
+int fdf_tracks_scratch_bytes(uint32_t n_frames, uint32_t width, uint32_t height,
+                             uint32_t min_dist, uint64_t t_cap, uint64_t c_cap, uint64_t* bytes) {
+    if (!bytes) return FDF_ERR_ARG;
+    TracksLayout L;
+    const int rc = tracks_layout(n_frames, width, height, min_dist, t_cap, c_cap, &L);
+    if (rc) return rc;
+    *bytes = n_frames ? L.total : 0;
+    return FDF_OK;
+}
+
+int fdf_tracks_update_device(fdf_ctx* ctx, uint32_t n_frames, const fdf_tracks_params* params,
+                             const int32_t* d_track_q11, const uint8_t* d_track_status,
+                             const uint32_t* d_track_ids, const uint32_t* d_track_ages,
+                             const uint64_t* d_track_offsets, uint64_t t_cap,
+                             const fdf_point* d_cand_points, const uint16_t* d_cand_scores,
+                             const uint64_t* d_cand_offsets, uint64_t c_cap, uint32_t* d_next_id,
+                             int32_t* d_out_q11, uint32_t* d_out_ids, uint32_t* d_out_ages,
+                             uint32_t* d_out_src, uint64_t out_cap, uint64_t* d_out_offsets,
+                             void* d_scratch, uint64_t scratch_bytes, void* stream) {
+    if (!ctx || !tracks_values_ok(params)) return FDF_ERR_ARG;
+    TracksLayout L;
+    const int rc = tracks_layout(n_frames, params->width, params->height, params->min_dist, t_cap,
+                                 c_cap, &L);
+    if (rc) return rc;
+    if (d_out_src && (t_cap > 0x7fffffffull || c_cap > 0x7fffffffull)) return FDF_ERR_ARG;
+    if (n_frames == 0) return FDF_OK;
+    if (!d_track_offsets || !d_cand_offsets || !d_next_id || !d_out_offsets || !d_scratch ||
+        scratch_bytes < L.total || !aligned_to(d_scratch, 256) ||
+        (t_cap && (!d_track_q11 || !d_track_ids || !d_track_ages)) ||
+        (c_cap && (!d_cand_points || !d_cand_scores)) ||
+        (out_cap && (!d_out_q11 || !d_out_ids || !d_out_ages)) ||
+        !aligned_to(d_track_q11, 8) || !aligned_to(d_cand_points, 8) || !aligned_to(d_out_q11, 8) ||
+        !aligned_to(d_track_offsets, 8) || !aligned_to(d_cand_offsets, 8) ||
+        !aligned_to(d_out_offsets, 8) || !aligned_to(d_track_ids, 4) ||
+        !aligned_to(d_track_ages, 4) || !aligned_to(d_next_id, 4) || !aligned_to(d_out_ids, 4) ||
+        !aligned_to(d_out_ages, 4) || !aligned_to(d_out_src, 4) || !aligned_to(d_cand_scores, 2))
+        return FDF_ERR_ARG;
+    DeviceGuard guard(ctx->device);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    uint8_t* base = static_cast<uint8_t*>(d_scratch);
+    fdfk::TracksParams p{};
+    p.n_frames = n_frames;
+    p.width = params->width;
+    p.height = params->height;
+    p.min_dist = params->min_dist;
+    p.margin = params->margin;
+    p.max_tracks = params->max_tracks;
+    p.passes = params->passes;
+    p.cell = L.cell;
+    p.cells_x = L.cells_x;
+    p.cells_y = L.cells_y;
+    p.t_q11 = reinterpret_cast<const int2*>(d_track_q11);
+    p.t_status = d_track_status;
+    p.t_ids = d_track_ids;
+    p.t_ages = d_track_ages;
+    p.c_pts = reinterpret_cast<const uint2*>(d_cand_points);
+    p.c_scores = d_cand_scores;
+    auto list = [&](fdfk::TracksList& l, const TracksListLayout& at, const uint64_t* offs,
+                    uint64_t cap) {
+        l.offs = offs;
+        l.cap = cap;
+        l.cursor = reinterpret_cast<uint32_t*>(base + at.cursor);
+        l.start = reinterpret_cast<uint32_t*>(base + at.start);
+        l.ent = reinterpret_cast<uint4*>(base + at.ent);
+        l.st[0] = base + at.st0;
+        l.st[1] = base + at.st1;
+        l.flag = base + at.flag;
+        // about two passes of a workgroup's threads per stream of average length
+        l.chunks = (uint32_t)std::min<uint64_t>(1024, cap / n_frames / (2 * fdfk::kTracksThreads) + 1);
+    };
+    list(p.t, L.t, d_track_offsets, t_cap);
+    list(p.c, L.c, d_cand_offsets, c_cap);
+    p.next_id = d_next_id;
+    p.kept = reinterpret_cast<uint32_t*>(base + L.kept);
+    p.n_new = reinterpret_cast<uint32_t*>(base + L.n_new);
+    p.id_base = reinterpret_cast<uint32_t*>(base + L.id_base);
+    p.tot = reinterpret_cast<uint64_t*>(base + L.tot);
+    p.out_q11 = reinterpret_cast<int2*>(d_out_q11);
+    p.out_ids = d_out_ids;
+    p.out_ages = d_out_ages;
+    p.out_src = d_out_src;
+    p.out_cap = out_cap;
+    p.out_offs = d_out_offsets;
+    const uint64_t cursor_bytes = sizeof(uint32_t) * (uint64_t)L.cells_x * L.cells_y * n_frames;
+    hipError_t e = hipMemsetAsync(p.t.cursor, 0, cursor_bytes, s);
+    if (e == hipSuccess) e = hipMemsetAsync(p.c.cursor, 0, cursor_bytes, s);
+    if (e == hipSuccess && t_cap) e = hipMemsetAsync(p.t.flag, 0, t_cap, s);
+    if (e == hipSuccess && c_cap) e = hipMemsetAsync(p.c.flag, 0, c_cap, s);
+    if (e == hipSuccess) e = fdfk::launch_tracks_update(p, s);
+    return status_of(e);
+}
+
+int fdf_tracks_update_points(fdf_ctx* ctx, const fdf_tracks_params* params,
+                             const int32_t* track_q11, const uint8_t* track_status,
+                             const uint32_t* track_ids, const uint32_t* track_ages,
+                             size_t n_tracks, const fdf_point* cand_points,
+                             const uint16_t* cand_scores, size_t n_cands, uint32_t* next_id,
+                             int32_t* out_q11, uint32_t* out_ids, uint32_t* out_ages,
+                             uint32_t* out_src, size_t cap, size_t* n_out) {
+    if (!ctx || !n_out || !next_id || !tracks_values_ok(params)) return FDF_ERR_ARG;
+    if (n_tracks && (!track_q11 || !track_ids || !track_ages)) return FDF_ERR_ARG;
+    if (n_cands && (!cand_points || !cand_scores)) return FDF_ERR_ARG;
+    if (cap && (!out_q11 || !out_ids || !out_ages)) return FDF_ERR_ARG;
+    if (out_src && (n_tracks > 0x7fffffffull || n_cands > 0x7fffffffull)) return FDF_ERR_ARG;
+    TracksLayout L;
+    const int rc = tracks_layout(1, params->width, params->height, params->min_dist, n_tracks,
+                                 n_cands, &L);
+    if (rc) return rc;
+    *n_out = 0;
+    Arena a(ctx);
+    const auto d_q11 = a.part<uint64_t>(n_tracks);
+    const auto d_status = a.part<uint8_t>(track_status ? n_tracks : 0);
+    const auto d_ids = a.part<uint32_t>(n_tracks);
+    const auto d_ages = a.part<uint32_t>(n_tracks);
+    const auto d_toffs = a.part<uint64_t>(2);
+    const auto d_cand = a.part<fdf_point>(n_cands);
+    const auto d_scores = a.part<uint16_t>(n_cands);
+    const auto d_coffs = a.part<uint64_t>(2);
+    const auto d_next = a.part<uint32_t>(1);
+    const auto d_oq11 = a.part<uint64_t>(cap);
+    const auto d_oids = a.part<uint32_t>(cap);
+    const auto d_oages = a.part<uint32_t>(cap);
+    const auto d_osrc = a.part<uint32_t>(out_src ? cap : 0);
+    const auto d_ooffs = a.part<uint64_t>(2);
+    const auto d_scratch = a.part<uint8_t>(L.total);
+    if (a.open() != FDF_OK) return FDF_ERR_ALLOC;
+    const uint64_t toffs[2] = {0, n_tracks}, coffs[2] = {0, n_cands};   // live until close()
+    if (n_tracks) {
+        a.upload(d_q11, reinterpret_cast<const uint64_t*>(track_q11));
+        if (track_status) a.upload(d_status, track_status);
+        a.upload(d_ids, track_ids);
+        a.upload(d_ages, track_ages);
+    }
+    if (n_cands) {
+        a.upload(d_cand, cand_points);
+        a.upload(d_scores, cand_scores);
+    }
+    a.upload(d_toffs, toffs);
+    a.upload(d_coffs, coffs);
+    a.upload(d_next, next_id);
+    if (a.ok()) {
+        const int status = fdf_tracks_update_device(
+            ctx, 1, params, reinterpret_cast<const int32_t*>(a.at(d_q11)),
+            track_status ? a.at(d_status) : nullptr, a.at(d_ids), a.at(d_ages), a.at(d_toffs),
+            n_tracks, a.at(d_cand), a.at(d_scores), a.at(d_coffs), n_cands, a.at(d_next),
+            reinterpret_cast<int32_t*>(a.at(d_oq11)), a.at(d_oids), a.at(d_oages),
+            out_src ? a.at(d_osrc) : nullptr, cap, a.at(d_ooffs), a.at(d_scratch), L.total,
+            ctx->stream);
+        if (status != FDF_OK) return status;
+    }
+    // two phases: the offsets tell how many entries to copy
+    uint64_t offs[2] = {0, 0};
+    uint32_t next = *next_id;
+    a.download(offs, d_ooffs, 2);
+    a.download(&next, d_next, 1);
+    a.note(hipStreamSynchronize(ctx->stream));
+    const uint64_t total = a.ok() ? offs[1] : 0;
+    const uint64_t ncopy = std::min<uint64_t>(total, cap);
+    if (ncopy) {
+        a.download(reinterpret_cast<uint64_t*>(out_q11), d_oq11, ncopy);
+        a.download(out_ids, d_oids, ncopy);
+        a.download(out_ages, d_oages, ncopy);
+        if (out_src) a.download(out_src, d_osrc, ncopy);
+    }
+    if (a.close() != FDF_OK) return FDF_ERR_DEVICE;
+    *next_id = next;
+    *n_out = (size_t)total;
+    return total > cap ? FDF_ERR_CAPACITY : FDF_OK;
 }
 
 // ---- brute-force Hamming matching (fdf_match.hip) ------------------------------------------

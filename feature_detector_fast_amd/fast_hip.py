@@ -2200,6 +2200,221 @@ def track_array(img0, img1, points, n_levels=3, scale=(2, 1), radius=10, max_ite
                        info >> 8)
 
 
+# Track-set maintenance between two tracking calls (fdf_tracks.hip; include/fdf.h has the rule).
+
+TRACKS_NEW = _native.FDF_TRACKS_NEW
+TrackSetResult = collections.namedtuple("TrackSetResult", "q11 ids ages src next_id")
+
+
+def _tracks_params(shape, min_dist, margin, max_tracks, passes):
+    h, w = (int(v) for v in shape)
+    min_dist, margin, max_tracks, passes = int(min_dist), int(margin), int(max_tracks), int(passes)
+    if not (1 <= w <= 65535 and 1 <= h <= 65535):
+        raise ValueError("shape must be (height, width) with sides in 1..65535")
+    if not 1 <= min_dist <= 255:
+        raise ValueError("min_dist must be in 1..255")
+    if margin < 0 or 2 * margin >= min(w, h):
+        raise ValueError("margin must satisfy 0 <= 2 * margin < min(width, height)")
+    if not 1 <= max_tracks <= 0xffffffff:
+        raise ValueError("max_tracks must be at least 1")
+    if not 1 <= passes <= 32:
+        raise ValueError("passes must be in 1..32")
+    return _native.FdfTracksParams(w, h, min_dist, margin, max_tracks, passes)
+
+
+def tracks_scratch_bytes(n_frames, shape, min_dist, t_cap, c_cap):
+    """Scratch bytes tracks_update_device needs (fdf_tracks_scratch_bytes; host only, no
+    device): ``shape`` is (height, width), ``t_cap`` and ``c_cap`` the capacities of the track
+    and the candidate arrays."""
+    h, w = (int(v) for v in shape)
+    v = ctypes.c_uint64()
+    check(_native.load().fdf_tracks_scratch_bytes(int(n_frames), w, h, int(min_dist), int(t_cap),
+                                                  int(c_cap), ctypes.byref(v)),
+          "fdf_tracks_scratch_bytes")
+    return v.value
+
+
+def _check_words(t, name, rows):
+    if t.dim() != 1 or t.element_size() != 4 or t.is_floating_point() or not t.is_contiguous() or \
+            t.numel() < rows:
+        raise ValueError(f"{name} must be a contiguous 32-bit integer tensor with {rows} entries")
+
+
+def tracks_update_device(track_q11, track_ids, track_ages, track_offsets, cand_points, cand_scores,
+                         cand_offsets, next_id, out_q11, out_ids, out_ages, out_offsets, shape,
+                         min_dist=16, margin=11, max_tracks=1024, passes=8, track_status=None,
+                         out_src=None, scratch=None, stream=None):
+    """The step between two track_device calls, on the device (fdf_tracks_update_device), for the
+    F streams ``track_offsets`` and ``cand_offsets`` (int64, F+1 entries each) describe: lost
+    tracks (``track_status`` 0, optional) and tracks within ``margin`` pixels of the border are
+    dropped, of two tracks within ``min_dist`` pixels the older stays, and the strongest
+    candidates that no survivor and no stronger admitted candidate is within ``min_dist`` of refill
+    each stream up to ``max_tracks``; ``passes`` bounds the suppression passes (8 converges on
+    real frames).  ``track_q11`` (t_cap, 2) int32 as track_device wrote next_q11, ``track_ids``
+    and ``track_ages`` (t_cap,) 32-bit, ``cand_points`` (c_cap, 2) and ``cand_scores`` (c_cap,)
+    16-bit as detect_device and score_device filled them, ``next_id`` (F,) 32-bit (read and
+    advanced), ``shape`` = (height, width).
+
+    Outputs: ``out_q11`` (out_cap, 2) int32, ``out_ids``, ``out_ages`` and the optional ``out_src``
+    (out_cap,) 32-bit (a survivor's track index, TRACKS_NEW | candidate index for a new track),
+    ``out_offsets`` (F+1,) int64 with the full totals.  ``out_q11`` and ``out_offsets`` are
+    ``coords="q11"`` points of the next track_device call.  ``scratch``: a uint8 CUDA tensor of
+    tracks_scratch_bytes(...) bytes (None: allocated through torch).  Asynchronous on ``stream``
+    (default: torch's current stream)."""
+    import torch
+
+    params = _tracks_params(shape, min_dist, margin, max_tracks, passes)
+    _check_offsets(torch, track_offsets, 1, "track_offsets")
+    f = track_offsets.numel() - 1
+    _check_offsets(torch, cand_offsets, f + 1, "cand_offsets")
+    _check_offsets(torch, out_offsets, f + 1, "out_offsets")
+    _check_points(track_q11, "track_q11", "t_cap")
+    _check_points(cand_points, "cand_points", "c_cap")
+    _check_points(out_q11, "out_q11", "out_cap")
+    t_cap, c_cap, out_cap = track_q11.shape[0], cand_points.shape[0], out_q11.shape[0]
+    for t, name, rows in ((track_ids, "track_ids", t_cap), (track_ages, "track_ages", t_cap),
+                          (next_id, "next_id", f), (out_ids, "out_ids", out_cap),
+                          (out_ages, "out_ages", out_cap), (out_src, "out_src", out_cap)):
+        if t is not None:
+            _check_words(t, name, rows)
+    if cand_scores.dim() != 1 or cand_scores.element_size() != 2 or \
+            cand_scores.is_floating_point() or not cand_scores.is_contiguous() or \
+            cand_scores.numel() < c_cap:
+        raise ValueError("cand_scores must be a contiguous 16-bit integer tensor with c_cap entries")
+    if track_status is not None and (track_status.dtype != torch.uint8 or track_status.dim() != 1 or
+                                     track_status.numel() < t_cap or
+                                     not track_status.is_contiguous()):
+        raise ValueError("track_status must be a contiguous uint8 tensor with t_cap entries")
+    if scratch is not None and (scratch.dtype != torch.uint8 or not scratch.is_contiguous()):
+        raise ValueError("scratch must be a contiguous uint8 tensor")
+    tensors = [track_q11, track_ids, track_ages, track_offsets, cand_points, cand_scores,
+               cand_offsets, next_id, out_q11, out_ids, out_ages, out_offsets]
+    tensors += [t for t in (track_status, out_src, scratch) if t is not None]
+    _check_one_device("tracks_update_device", tensors)
+    need = tracks_scratch_bytes(f, shape, min_dist, t_cap, c_cap)
+    current = torch.cuda.current_stream(track_offsets.device)
+    if stream is None:
+        stream = current
+    if scratch is None:
+        scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=track_offsets.device)
+        if stream != current:
+            scratch.record_stream(stream)    # in use on `stream` until the call's kernels are done
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+    rc = _native.load().fdf_tracks_update_device(
+        context(track_offsets.device.index).handle, f, ctypes.byref(params), ptr(track_q11),
+        ptr(track_status), ptr(track_ids), ptr(track_ages), ptr(track_offsets), t_cap,
+        ptr(cand_points), ptr(cand_scores), ptr(cand_offsets), c_cap, ptr(next_id), ptr(out_q11),
+        ptr(out_ids), ptr(out_ages), ptr(out_src), out_cap, ptr(out_offsets), scratch.data_ptr(),
+        scratch.numel(), ctypes.c_void_p(stream.cuda_stream))
+    check(rc, "fdf_tracks_update_device")
+
+
+def update_tracks(shape, track_q11, track_ids, track_ages, cand_points, cand_scores, next_id=0,
+                  min_dist=16, margin=11, max_tracks=1024, passes=8, status=None, device=0):
+    """One stream's track set updated from host arrays (fdf_tracks_update_points): ``track_q11``
+    (T, 2) positions in 1/2048 pixel, ``track_ids`` and ``track_ages`` (T,), ``status`` (T,)
+    optional, ``cand_points`` (C, 2) pixels and ``cand_scores`` (C,).  Returns a
+    :class:`TrackSetResult`: ``q11`` (K, 2) int32, ``ids``, ``ages`` and ``src`` (K,) uint32 (a
+    survivor's index, TRACKS_NEW | candidate index for a new track) and the advanced ``next_id``."""
+    params = _tracks_params(shape, min_dist, margin, max_tracks, passes)
+    q = np.ascontiguousarray(np.asarray(track_q11).reshape(-1, 2), dtype=np.int32)
+    ids = np.ascontiguousarray(track_ids, dtype=np.uint32).reshape(-1)
+    ages = np.ascontiguousarray(track_ages, dtype=np.uint32).reshape(-1)
+    cand = _host_points(np.asarray(cand_points).reshape(-1, 2))
+    scores = np.ascontiguousarray(cand_scores, dtype=np.uint16).reshape(-1)
+    st = None if status is None else np.ascontiguousarray(status, dtype=np.uint8).reshape(-1)
+    nt, nc = len(q), len(cand)
+    if len(ids) != nt or len(ages) != nt or len(scores) != nc or (st is not None and len(st) != nt):
+        raise ValueError("the arrays of a list must have one entry per point")
+    cap = nt + min(nc, params.max_tracks)
+    out_q = np.empty((cap, 2), dtype=np.int32)
+    out_ids, out_ages, out_src = (np.empty(cap, dtype=np.uint32) for _ in range(3))
+    nid = ctypes.c_uint32(int(next_id) & 0xffffffff)
+    n = ctypes.c_size_t(0)
+    ptr = lambda t: t.ctypes.data if t is not None and t.size else None
+    rc = _native.load().fdf_tracks_update_points(
+        context(device).handle, ctypes.byref(params), ptr(q), ptr(st), ptr(ids), ptr(ages), nt,
+        ptr(cand), ptr(scores), nc, ctypes.byref(nid), ptr(out_q), ptr(out_ids), ptr(out_ages),
+        ptr(out_src), cap, ctypes.byref(n))
+    check(rc, "fdf_tracks_update_points")
+    k = n.value
+    return TrackSetResult(out_q[:k], out_ids[:k], out_ages[:k], out_src[:k], nid.value)
+
+
+def track_sequence_array(frames, config, min_dist=16, margin=None, max_tracks=1024, passes=8,
+                         n_levels=3, scale=(2, 1), radius=10, max_iters=30, eps=20, min_eig=1.0,
+                         device=0):
+    """A whole detect + track loop over the host video ``frames`` ((F, H, W) uint8) on the device.
+    Frame 0: detect_device + score_device, then tracks_update_device on an empty set.  Every later
+    frame k: track_device from frame k - 1 (over a pyramid of ``n_levels`` levels at ``scale``),
+    then tracks_update_device with frame k's detections as candidates.  ``margin`` defaults to
+    ``radius + 1``.  Ids start at 0.  Only the detection counts are read back before the loop;
+    the loop itself never leaves the device.  Returns one (ids (K,) uint32, q11 (K, 2) int32, ages
+    (K,) uint32) triple per frame: the track set after that frame's update."""
+    import torch
+
+    arr = np.ascontiguousarray(frames)
+    if arr.ndim != 3 or arr.dtype != np.uint8:
+        raise ValueError("frames must be a (F, H, W) uint8 array")
+    f, h, w = arr.shape
+    margin = int(radius) + 1 if margin is None else margin
+    params = _tracks_params((h, w), min_dist, margin, max_tracks, passes)
+    radius, max_iters, eps, min_eig = _track_values(radius, max_iters, eps, min_eig)
+    if f == 0:
+        return []
+    dev = torch.device("cuda", device)
+    with torch.cuda.device(dev):
+        d_frames = torch.from_numpy(arr).to(dev)
+        pyr = Pyramid(d_frames, n_levels, scale)
+        cap = capacity_guess(h * w) * f
+        while True:
+            pts = torch.empty((cap, 2), dtype=torch.int32, device=dev)
+            offs = torch.zeros(f + 1, dtype=torch.int64, device=dev)
+            detect_device(d_frames, config, pts, offs)
+            total = int(offs[f])
+            if total <= cap:
+                break
+            cap = total
+        scores = torch.empty(max(cap, 1), dtype=torch.int16, device=dev)
+        score_device(d_frames, config, pts, offs, scores)
+        bounds = offs.cpu().tolist()
+        # frame k's candidates as one stream of their own: offsets {0, n_k}
+        c_offs = torch.tensor([[0, bounds[k + 1] - bounds[k]] for k in range(f)],
+                              dtype=torch.int64, device=dev)
+        m = params.max_tracks = min(params.max_tracks, 1 << 24)
+        q11 = torch.empty((f, m, 2), dtype=torch.int32, device=dev)
+        ids = torch.empty((f, m), dtype=torch.int32, device=dev)
+        ages = torch.empty((f, m), dtype=torch.int32, device=dev)
+        t_offs = torch.zeros((f + 1, 2), dtype=torch.int64, device=dev)   # row 0: the empty set
+        moved_q11 = torch.empty((m, 2), dtype=torch.int32, device=dev)
+        status = torch.empty(m, dtype=torch.uint8, device=dev)
+        next_id = torch.zeros(1, dtype=torch.int32, device=dev)
+        n_c = max(bounds[k + 1] - bounds[k] for k in range(f))
+        scratch = torch.empty(max(tracks_scratch_bytes(1, (h, w), min_dist, m, n_c), 1),
+                              dtype=torch.uint8, device=dev)
+        for k in range(f):
+            cand = pts[bounds[k]:bounds[k + 1]]
+            cand_scores = scores[bounds[k]:bounds[k + 1]]
+            if k == 0:
+                prev = (q11[0, :0], ids[0, :0], ages[0, :0])
+                st = None
+            else:
+                track_device(pyr, pyr, q11[k - 1], t_offs[k], moved_q11, status, prev_first=k - 1,
+                             next_first=k, n_frames=1, coords="q11", radius=radius,
+                             max_iters=max_iters, eps=eps, min_eig=min_eig)
+                prev = (moved_q11, ids[k - 1], ages[k - 1])
+                st = status
+            tracks_update_device(prev[0], prev[1], prev[2], t_offs[k], cand, cand_scores, c_offs[k],
+                                 next_id, q11[k], ids[k], ages[k], t_offs[k + 1], (h, w),
+                                 min_dist=min_dist, margin=margin, max_tracks=m, passes=passes,
+                                 track_status=None if st is None else st[:prev[0].shape[0]],
+                                 scratch=scratch)
+        counts = t_offs[:, 1].cpu().tolist()
+        h_q11, h_ids, h_ages = q11.cpu().numpy(), ids.cpu().numpy(), ages.cpu().numpy()
+    return [(h_ids[k, :counts[k + 1]].view(np.uint32).copy(), h_q11[k, :counts[k + 1]].copy(),
+             h_ages[k, :counts[k + 1]].view(np.uint32).copy()) for k in range(f)]
+
+
 __all__ = ["NORTH", "EAST", "SOUTH", "WEST", "circle", "calculate_offsets", "context",
            "shard_contexts", "capacity_guess", "Lanes",
            "detect_array", "detector", "detector_batch", "detect_device", "keypoint_scores",
@@ -2220,6 +2435,8 @@ __all__ = ["NORTH", "EAST", "SOUTH", "WEST", "circle", "calculate_offsets", "con
            "warp_device", "warp_array", "model_invert",
            "TRACK_REASONS", "TrackResult", "track_device", "track_array", "track_map_position",
            "track_map_displacement",
+           "TRACKS_NEW", "TrackSetResult", "tracks_scratch_bytes", "tracks_update_device",
+           "update_tracks", "track_sequence_array",
            "detect_rgb_array", "detector_rgb", "rgb_to_luma", "detect_device_rgb",
            "score_rings", "score_rings_device", "keypoint_score_max_threshold",
            "keypoint_score_sum_abs_difference", "NonMaximalSuppression"]

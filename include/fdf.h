@@ -1202,6 +1202,114 @@ int fdf_track_frames(fdf_ctx* ctx, const uint8_t* prev, const uint8_t* next, uin
                      uint32_t* out_info);
 
 /*
+ * Track-set maintenance between two tracking calls (extension; the reference has no tracks).
+ * What a video front end does between "track" and "track again": drop lost and border tracks,
+ * keep the older of two tracks that drifted onto one corner, add the strongest fresh corners that
+ * no surviving track is near, up to a budget, give them new ids and hand one compact list to the
+ * next fdf_track_device call.  All arithmetic is integer; the result is a pure function of the
+ * inputs (atomics only count, or claim slots whose order nothing reads).
+ *
+ * Indexing.  n_frames independent streams (cameras, or the frames of a batch) are updated by one
+ * call.  As in fdf_orient_device, stream f owns the tracks [t_offs[f], min(t_offs[f+1], t_cap))
+ * and the candidates [c_offs[f], min(c_offs[f+1], c_cap)).  Priorities and d_out_src use the
+ * global array indices.
+ *
+ * Inputs.  Tracks: d_track_q11 (two int32 each, 1/2048 pixel, as fdf_track_device writes
+ * d_next_q11), d_track_status (u8, optional: NULL = every track is tracked), d_track_ids and
+ * d_track_ages (u32).  Candidates: d_cand_points (fdf_point, in any order) and d_cand_scores
+ * (u16), e.g. fdf_detect_device + fdf_score_device of the new frame.  d_next_id (u32 per stream,
+ * in and out): the stream's next unused id.  Parameters (fdf_tracks_params): width, height 1..65535
+ * (level 0), min_dist 1..255 pixels, margin with 2 * margin < min(width, height) (the tracker's
+ * radius + 1 is the usual value), max_tracks >= 1 (per stream), passes 1..32.
+ *
+ *   1. Alive.  A track is alive iff its status byte is non-zero, margin * 2048 <= X <=
+ *      (width - 1 - margin) * 2048 and margin * 2048 <= Y <= (height - 1 - margin) * 2048; a lost
+ *      track (-1, -1) fails that by itself.  A candidate is eligible iff margin <= x <= width - 1 -
+ *      margin and margin <= y <= height - 1 - margin.
+ *   2. Pixel.  A track's pixel is px = (X + 1024) >> 11, py = (Y + 1024) >> 11.  Two points are
+ *      near iff dx^2 + dy^2 < min_dist^2 (strict: (3, 4) is not near at min_dist 5, near at 6).
+ *   3. Suppression by passes, the same for both lists.  A point is undecided (0), admitted (1) or
+ *      rejected (2).  j dominates i iff j is near i, of the same stream and list, and of higher
+ *      priority: tracks by larger age, then lower index; candidates by larger score, then lower
+ *      index (a total order).  Pass p reads the states of pass p - 1 only: an undecided point
+ *      becomes rejected if some dominator was admitted, else admitted if every dominator was
+ *      rejected, else stays undecided.  After `passes` passes an undecided point is dropped.  Pass
+ *      1 admits exactly the local maxima within min_dist; at convergence the admitted set is the
+ *      sequential greedy selection in priority order (OpenCV's minDistance rule).
+ *   4. Tracks.  Alive tracks start undecided, all others rejected; the kept survivors are the
+ *      tracks admitted after the passes.
+ *   5. Candidates.  An eligible candidate near no kept survivor starts undecided, all others
+ *      rejected.  After the passes free[f] = max(0, max_tracks - kept[f]); of stream f's admitted
+ *      candidates those of rank < free[f] become new tracks, the rank by score descending, ties
+ *      to the lower index (fdf_select_device's rule over the whole frame).  max_tracks never
+ *      removes a survivor.
+ *   6. Output per stream: the kept survivors in track index order (position copied unchanged, id
+ *      carried, age min(age + 1, 0xFFFFFFFF)), then the new tracks in candidate index order
+ *      (position (x * 2048, y * 2048), age 0, the j-th new track's id next_id[f] + j modulo 2^32);
+ *      next_id[f] then advances by the stream's full count of new tracks.
+ *   7. Arrays: d_out_q11, d_out_ids, d_out_ages; optional d_out_src (u32: a survivor's track
+ *      index, FDF_TRACKS_NEW | candidate index for a new track).  d_out_offsets (n_frames + 1
+ *      entries) is the exclusive prefix of the streams' totals with the full total last, also
+ *      beyond out_cap, as fdf_detect_device and fdf_select_device do; entries at or past
+ *      min(total, out_cap) are never written.  d_out_q11 with d_out_offsets are FDF_COORDS_Q11
+ *      points of fdf_track_device as they are.
+ *
+ * Example.  32 x 24, min_dist 5, margin 2, max_tracks 4, passes 8, next_id 7.  Tracks (X, Y; id;
+ * age; status): 0 (20480, 20480; 3; 5; 1), 1 (15359, 28672; 4; 2; 1), 2 (22528, 20480; 5; 9; 1),
+ * 3 (-1, -1; 6; 1; 0).  Pixels (10, 10), (7, 14) (X = 15360 would give 8), (11, 10); track 3 is
+ * not alive.  Track 2 is near track 0 and older: pass 1 admits tracks 1 and 2, pass 2 rejects
+ * track 0 ((7, 14) is at distance^2 25 of (10, 10): not near).  Candidates (x, y; score):
+ * 0 (12, 10; 90) is near survivor 2; 1 (20, 10; 50); 2 (23, 14; 50), at distance^2 25 of
+ * candidate 1; 3 (21, 11; 40), dominated by candidate 1; 4 (1, 12; 99), inside the margin;
+ * 5 (28, 20; 10).  Admitted: 1, 2, 5; free = 4 - 2 = 2 takes 1 and 2.  Output (X, Y; id; age;
+ * src): (15359, 28672; 4; 3; 1), (22528, 20480; 5; 10; 2), (40960, 20480; 7; 0; 0x80000001),
+ * (47104, 28672; 8; 0; 0x80000002); offsets {0, 4}; next_id 9.
+ *
+ * fdf_tracks_update_device: asynchronous on `stream` (NULL = the HIP null stream); takes no
+ * context lock, uses no workspace, allocates nothing; it only binds the context's device.  Its
+ * memsets run on the stream.  d_scratch holds fdf_tracks_scratch_bytes(...) bytes, 256-byte
+ * aligned.  Whatever the positions, offsets and candidates hold, no access leaves the given
+ * arrays: index ranges are clamped to the caps and cell indices to the grid.  FDF_ERR_ARG,
+ * synchronously and with nothing launched: a parameter out of range, n_frames > 65535, a cap above
+ * 2^32 - 1 (above 2^31 - 1 when d_out_src is given), a NULL required pointer (the track arrays
+ * when t_cap > 0, the candidate arrays when c_cap > 0, the output arrays when out_cap > 0, the
+ * offsets, d_next_id), misaligned arrays (positions, points and offsets 8 bytes; ids, ages,
+ * d_next_id and d_out_src 4; scores 2), scratch NULL, misaligned or too small.  n_frames == 0:
+ * FDF_OK, nothing written.
+ *
+ * fdf_tracks_scratch_bytes: host only (no device).  fdf_tracks_update_points: one stream of host
+ * arrays, synchronous; its buffers are allocated and freed by the call, the context's workspace
+ * and retained result stay untouched.  *next_id is read and advanced; *n_out is the stream's
+ * total; FDF_ERR_CAPACITY when that exceeds `cap` (the first `cap` entries are written).
+ */
+#define FDF_TRACKS_NEW 0x80000000u
+typedef struct fdf_tracks_params {
+    uint32_t width, height;   /* level 0 */
+    uint32_t min_dist;        /* 1..255 pixels */
+    uint32_t margin;          /* 2 * margin < min(width, height) */
+    uint32_t max_tracks;      /* >= 1, per stream */
+    uint32_t passes;          /* 1..32 */
+} fdf_tracks_params;
+int fdf_tracks_scratch_bytes(uint32_t n_frames, uint32_t width, uint32_t height,
+                             uint32_t min_dist, uint64_t t_cap, uint64_t c_cap, uint64_t* bytes);
+int fdf_tracks_update_device(fdf_ctx* ctx, uint32_t n_frames, const fdf_tracks_params* params,
+                             const int32_t* d_track_q11, const uint8_t* d_track_status,
+                             const uint32_t* d_track_ids, const uint32_t* d_track_ages,
+                             const uint64_t* d_track_offsets, uint64_t t_cap,
+                             const fdf_point* d_cand_points, const uint16_t* d_cand_scores,
+                             const uint64_t* d_cand_offsets, uint64_t c_cap, uint32_t* d_next_id,
+                             int32_t* d_out_q11, uint32_t* d_out_ids, uint32_t* d_out_ages,
+                             uint32_t* d_out_src, uint64_t out_cap, uint64_t* d_out_offsets,
+                             void* d_scratch, uint64_t scratch_bytes, void* stream);
+int fdf_tracks_update_points(fdf_ctx* ctx, const fdf_tracks_params* params,
+                             const int32_t* track_q11, const uint8_t* track_status,
+                             const uint32_t* track_ids, const uint32_t* track_ages,
+                             size_t n_tracks, const fdf_point* cand_points,
+                             const uint16_t* cand_scores, size_t n_cands, uint32_t* next_id,
+                             int32_t* out_q11, uint32_t* out_ids, uint32_t* out_ages,
+                             uint32_t* out_src, size_t cap, size_t* n_out);
+
+/*
  * Streaming host pipeline (extension; the reference's callers detect on one
  * host image at a time, src/lib.rs:62-64, src/main.rs:58-64).  Host frames in, host
  * keypoints out, with the host->device copy of one batch, the detection of another and the

@@ -24,6 +24,7 @@
 //   (none: ... over a scale pyramid) --                   fdf::resize, fdf::pyramid_plan, fdf::build_pyramid
 //   (none: ... and warp by the model) --                  fdf::warp, fdf::model_invert
 //   (none: ... or track the points)  --                   fdf::track
+//   (none: ... and keep the track set) --                 fdf::update_tracks
 //
 // Where the reference panics (n < 9, n > 16, degenerate sizes) these throw fdf::Error.
 // Each thread lazily owns one device context per HIP device (device 0 unless
@@ -536,6 +537,56 @@ inline Tracks track(const GrayView& prev, const GrayView& next, const std::vecto
 inline Tracks track(const GrayView& prev, const GrayView& next, const std::vector<Point>& points,
                     const TrackOptions& opt = TrackOptions()) {
     return track(prev, next, points, opt, thread_context());
+}
+
+// Track-set maintenance between two tracking calls (extension, fdf_tracks_update_points;
+// include/fdf.h has the rule): lost and border tracks are dropped, of two tracks within min_dist
+// the older stays, the strongest candidates no survivor is near refill the set up to max_tracks.
+// Entry k of every array belongs to track k; `src` is a survivor's index in the input set or
+// FDF_TRACKS_NEW | the candidate's index.  `next_id` is read and advanced.
+struct TrackSetOptions {
+    uint32_t min_dist = 16, margin = 11, max_tracks = 1024, passes = 8;
+};
+struct TrackSet {
+    std::vector<std::array<int32_t, 2>> q11;
+    std::vector<uint32_t> ids, ages, src;
+    std::vector<uint8_t> status;               // input only: empty means every track is tracked
+};
+inline TrackSet update_tracks(uint32_t width, uint32_t height, const TrackSet& tracks,
+                              const std::vector<Point>& candidates,
+                              const std::vector<uint16_t>& scores, uint32_t& next_id,
+                              const TrackSetOptions& opt, Context& ctx) {
+    const size_t nt = tracks.q11.size(), nc = candidates.size();
+    if (tracks.ids.size() != nt || tracks.ages.size() != nt || scores.size() != nc ||
+        (!tracks.status.empty() && tracks.status.size() != nt))
+        throw Error(FDF_ERR_ARG, "fdf::update_tracks: the arrays differ in length");
+    const fdf_tracks_params params{width, height, opt.min_dist, opt.margin, opt.max_tracks,
+                                   opt.passes};
+    TrackSet out;
+    size_t cap = nt + std::min<size_t>(nc, opt.max_tracks), n = 0;
+    out.q11.resize(cap);
+    out.ids.resize(cap);
+    out.ages.resize(cap);
+    out.src.resize(cap);
+    check(fdf_tracks_update_points(ctx.get(), &params, nt ? tracks.q11[0].data() : nullptr,
+                                   tracks.status.empty() ? nullptr : tracks.status.data(),
+                                   tracks.ids.data(), tracks.ages.data(), nt,
+                                   reinterpret_cast<const fdf_point*>(candidates.data()),
+                                   scores.data(), nc, &next_id, cap ? out.q11[0].data() : nullptr,
+                                   out.ids.data(), out.ages.data(), out.src.data(), cap, &n),
+          "fdf_tracks_update_points");
+    out.q11.resize(n);
+    out.ids.resize(n);
+    out.ages.resize(n);
+    out.src.resize(n);
+    return out;
+}
+inline TrackSet update_tracks(uint32_t width, uint32_t height, const TrackSet& tracks,
+                              const std::vector<Point>& candidates,
+                              const std::vector<uint16_t>& scores, uint32_t& next_id,
+                              const TrackSetOptions& opt = TrackSetOptions()) {
+    return update_tracks(width, height, tracks, candidates, scores, next_id, opt,
+                         thread_context());
 }
 
 inline std::vector<Point> detect(const GrayView& img, const Config& config) {
