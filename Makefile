@@ -6,7 +6,8 @@
 #                          fdf::select_best, fdf::keypoint_angles, fdf::keypoint_harris,
 #                          fdf::keypoint_descriptors,
 #                          fdf::match_descriptors, fdf::resize / fdf::build_pyramid,
-#                          fdf::estimate_model, fdf::refine_model, fdf::warp,
+#                          fdf::estimate_model, fdf::refine_model, fdf::estimate_fundamental,
+#                          fdf::warp,
 #                          fdf::track, fdf::update_tracks
 #   tests/cpp/test_wg_share  host-only check of the kernels' work split (fdf_common.h)
 #   tests/cpp/test_geometry  host-only table of the band geometry and launch plan (fdf_geometry.h)
@@ -20,9 +21,9 @@ CSRC := $(PKG)/csrc
 LIBFDF := $(PKG)/libfdf.so
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Iinclude $(EXTRA_HIPFLAGS)
 OBJS := $(addprefix $(CSRC)/fdf_,$(addsuffix .o,kernels sweep sweep_latency sweep_rgb select \
-	orient harris describe match ransac resize warp track tracks api stages pipeline))
+	orient harris describe match ransac fundamental resize warp track tracks api stages pipeline))
 HEADERS := $(wildcard $(CSRC)/*.h) include/fdf.h
-CPP_TESTS := $(addprefix tests/cpp/test_cpp_,api select orient harris describe match pyramid ransac refine warp track tracks)
+CPP_TESTS := $(addprefix tests/cpp/test_cpp_,api select orient harris describe match pyramid ransac refine fundamental warp track tracks)
 
 all: $(LIBFDF) oracle/liboracle.so oracle/libfast_avx2.so $(CPP_TESTS) tests/cpp/test_wg_share \
 	tests/cpp/test_geometry

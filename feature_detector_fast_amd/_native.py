@@ -51,7 +51,9 @@ EXPORTED_SYMBOLS = (
     "fdf_refine_scratch_bytes", "fdf_refine_device", "fdf_refine_points", "fdf_warp_device",
     "fdf_warp_frame", "fdf_model_invert", "fdf_track_device", "fdf_track_frames",
     "fdf_track_map_position", "fdf_track_map_displacement", "fdf_tracks_scratch_bytes",
-    "fdf_tracks_update_device", "fdf_tracks_update_points",
+    "fdf_tracks_update_device", "fdf_tracks_update_points", "fdf_fundamental_sample",
+    "fdf_fundamental_scratch_bytes", "fdf_fundamental_device", "fdf_fundamental_check_device",
+    "fdf_fundamental_points",
 )
 
 
@@ -330,6 +332,19 @@ def load():
     lib.fdf_tracks_update_points.argtypes = [vp, ctypes.POINTER(FdfTracksParams), vp, vp, vp, vp, sz,
                                              vp, vp, sz, ctypes.POINTER(u32), vp, vp, vp, vp, sz,
                                              ctypes.POINTER(sz)]
+    lib.fdf_fundamental_sample.restype = ctypes.c_int
+    lib.fdf_fundamental_sample.argtypes = [u32, u32, u32, u32, vp, ctypes.POINTER(u32)]
+    lib.fdf_fundamental_scratch_bytes.restype = ctypes.c_int
+    lib.fdf_fundamental_scratch_bytes.argtypes = [u32, u64, u32, ctypes.POINTER(u64)]
+    lib.fdf_fundamental_device.restype = ctypes.c_int
+    lib.fdf_fundamental_device.argtypes = [vp, u32, vp, vp, u64, vp, vp, vp, u64, vp, u32, u32,
+                                           ctypes.c_float, u32, vp, vp, vp, u64, vp]
+    lib.fdf_fundamental_check_device.restype = ctypes.c_int
+    lib.fdf_fundamental_check_device.argtypes = [vp, u32, vp, vp, u64, vp, vp, vp, u64, vp, u32, vp,
+                                                 ctypes.c_float, vp, vp, vp]
+    lib.fdf_fundamental_points.restype = ctypes.c_int
+    lib.fdf_fundamental_points.argtypes = [vp, vp, vp, sz, sz, vp, vp, u32, u32, ctypes.c_float,
+                                           u32, vp, vp]
     del u8p
     _lib = lib
     return lib

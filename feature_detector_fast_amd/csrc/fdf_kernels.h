@@ -549,7 +549,8 @@ constexpr uint32_t kRansacTile = 256;                 // correspondences of an L
 constexpr int kRansacWideWaves = 8;                   // waves that share a block's scoring in a small grid
 constexpr uint32_t kRansacWideMaxBlocks = 128;        // ... one of at most this many blocks: 1024 waves
 constexpr uint32_t kRansacMaxHyp = 65536;
-constexpr uint32_t kRansacMaxDraws = 16;              // draws a sample may take
+constexpr uint32_t kRansacMaxDraws = 16;              // draws a sample of 3 or 4 may take
+constexpr uint32_t kFundamentalMaxDraws = 32;         // ... and a sample of 8 (fdf_fundamental_device)
 constexpr uint32_t kRansacInvalid = 0xffffffffu;      // count of an invalid hypothesis; no best one
 constexpr uint32_t kRansacAffine = 0, kRansacHomography = 1;   // FDF_MODEL_*
 constexpr uint32_t kRansacU32 = 0, kRansacF32 = 1;             // FDF_COORDS_*
@@ -565,9 +566,9 @@ __host__ __device__ inline uint32_t ransac_start_state(uint32_t seed, uint32_t f
     return st ? st : 0x9E3779B9u;
 }
 // The first S distinct draws in idx[0..S) and true, or kRansacInvalid in all of idx and false after
-// kRansacMaxDraws draws; *draws
+// kDraws draws; *draws
 // (optional) gets the draws made.  Every index is a compile-time one: idx stays in registers.
-template <int S>
+template <int S, uint32_t kDraws = kRansacMaxDraws>
 __host__ __device__ inline bool ransac_sample(uint32_t seed, uint32_t frame, uint32_t hyp,
                                               uint32_t m, uint32_t (&idx)[S], uint32_t* draws) {
     uint32_t st = ransac_start_state(seed, frame, hyp);
@@ -575,7 +576,7 @@ __host__ __device__ inline bool ransac_sample(uint32_t seed, uint32_t frame, uin
     uint32_t d = 0;
 #pragma unroll
     for (int k = 0; k < S; ++k) idx[k] = kRansacInvalid;
-    while (d < kRansacMaxDraws && n < S) {
+    while (d < kDraws && n < S) {
         st ^= st << 13;
         st ^= st >> 17;
         st ^= st << 5;
@@ -614,6 +615,21 @@ struct RansacParams {
 };
 // compaction, hypothesis and finalisation kernels on `stream`
 hipError_t launch_ransac(const RansacParams& p, hipStream_t stream);
+// the compaction kernel alone (n_frames > 0): corr and n_corr from the correspondence arrays
+hipError_t launch_ransac_compact(const RansacParams& p, hipStream_t stream);
+
+// RANSAC fundamental-matrix estimation (fdf_fundamental.hip; fdf_fundamental_device): `model` is
+// unused, everything else is as above.
+constexpr int kFundamentalSample = 8;
+// compaction (fdf_ransac.hip's), hypothesis and finalisation kernels on `stream`
+hipError_t launch_fundamental(const RansacParams& p, hipStream_t stream);
+struct FundamentalCheckParams {
+    RansacParams r;              // the correspondence arrays; tt; models: the output (may be
+                                 // models_in); inliers; no scratch
+    const double* models_in;     // n_frames fdf_model
+};
+// one kernel on `stream`: the caller's matrices recounted (fdf_fundamental_check_device)
+hipError_t launch_fundamental_check(const FundamentalCheckParams& p, hipStream_t stream);
 
 // Least-squares refinement of the models over their inliers (fdf_ransac.hip; fdf_refine_device).
 constexpr uint32_t kRefineMaxRounds = 8;

@@ -50,36 +50,13 @@
 
 #include "fdf_common.h"
 #include "fdf_kernels.h"
+#include "fdf_ransac_impl.h"
 
 #pragma clang fp contract(off)
 
 namespace fdfk {
 
 namespace {
-
-constexpr double kRansacMinPivot = 0x1p-20;
-
-struct Corr { double x, y, u, v; };
-
-// The bits of a coordinate as a double: exact for both types.
-__device__ __forceinline__ double coord(uint32_t bits, uint32_t coords) {
-    return coords == kRansacF32 ? (double)__uint_as_float(bits) : (double)bits;
-}
-
-// Is query i (inside the frame's query range) a correspondence of the frame whose train range is
-// `tr`?  Yes: *c holds it.  The match's index is compared with the range before t_coords is read.
-__device__ __forceinline__ bool correspondence(const RansacParams& P, uint64_t i, IndexRange tr,
-                                               Corr* c) {
-    if (P.keep && P.keep[i] == 0) return false;
-    const uint32_t j = P.matches[i].x;
-    if (j == kMatchNone || j < tr.lo || j >= tr.hi) return false;
-    const uint2 q = P.q_coords[i], t = P.t_coords[j];
-    c->x = coord(q.x, P.coords);
-    c->y = coord(q.y, P.coords);
-    c->u = coord(t.x, P.coords);
-    c->v = coord(t.y, P.coords);
-    return true;
-}
 
 __global__ __launch_bounds__(kRansacFrameThreads) void ransac_compact_kernel(RansacParams P) {
     __shared__ uint32_t s_wave[kRansacFrameThreads / 64];
@@ -588,6 +565,11 @@ __global__ __launch_bounds__(kRansacFrameThreads) void refine_kernel(RefineParam
 }
 
 }  // namespace
+
+hipError_t launch_ransac_compact(const RansacParams& p, hipStream_t stream) {
+    hipLaunchKernelGGL(ransac_compact_kernel, dim3(p.n_frames), dim3(kRansacFrameThreads), 0, stream, p);
+    return hipGetLastError();
+}
 
 hipError_t launch_refine(const RefineParams& p, hipStream_t stream) {
     const RansacParams& r = p.r;

@@ -1748,4 +1748,148 @@ int fdf_refine_points(fdf_ctx* ctx, const void* q_coords, const void* t_coords, 
     return a.close();
 }
 
+// ---- RANSAC fundamental-matrix estimation (fdf_fundamental.hip) -------------------------------
+namespace {
+
+// What the fundamental entries check of the values.
+inline bool fundamental_values_ok(uint32_t coords, float threshold) {
+    return ransac_values_ok(coords, FDF_MODEL_HOMOGRAPHY, threshold);
+}
+
+// The correspondence arrays of a call, as the kernels take them.
+fdfk::RansacParams fundamental_params(uint32_t n_frames, const fdf_match* d_matches,
+                                      const uint8_t* d_keep, uint64_t q_cap,
+                                      const uint64_t* d_q_offsets, const void* d_q_coords,
+                                      const void* d_t_coords, uint64_t t_cap,
+                                      const uint64_t* d_t_offsets, uint32_t coords,
+                                      float threshold, fdf_model* d_models, uint8_t* d_inliers) {
+    fdfk::RansacParams p{};
+    p.matches = reinterpret_cast<const uint2*>(d_matches);
+    p.keep = d_keep;
+    p.q_offs = d_q_offsets;
+    p.q_cap = q_cap;
+    p.q_coords = static_cast<const uint2*>(d_q_coords);
+    p.t_coords = static_cast<const uint2*>(d_t_coords);
+    p.t_offs = d_t_offsets;
+    p.t_cap = t_cap;
+    p.n_frames = n_frames;
+    p.coords = coords;
+    p.tt = (double)threshold * (double)threshold;
+    p.models = reinterpret_cast<double*>(d_models);
+    p.inliers = d_inliers;
+    return p;
+}
+
+}  // namespace
+
+int fdf_fundamental_sample(uint32_t seed, uint32_t frame, uint32_t hypothesis, uint32_t m,
+                           uint32_t idx[8], uint32_t* draws) {
+    if (!idx) return FDF_ERR_ARG;
+    uint32_t got[fdfk::kFundamentalSample];
+    fdfk::ransac_sample<fdfk::kFundamentalSample, fdfk::kFundamentalMaxDraws>(seed, frame, hypothesis,
+                                                                            m, got, draws);
+    std::memcpy(idx, got, sizeof(got));
+    return FDF_OK;
+}
+
+int fdf_fundamental_scratch_bytes(uint32_t n_frames, uint64_t q_cap, uint32_t n_hyp,
+                                  uint64_t* bytes) {
+    return fdf_ransac_scratch_bytes(n_frames, q_cap, n_hyp, bytes);
+}
+
+int fdf_fundamental_device(fdf_ctx* ctx, uint32_t n_frames, const fdf_match* d_matches,
+                           const uint8_t* d_keep, uint64_t q_cap, const uint64_t* d_q_offsets,
+                           const void* d_q_coords, const void* d_t_coords, uint64_t t_cap,
+                           const uint64_t* d_t_offsets, uint32_t coords, uint32_t n_hyp,
+                           float threshold, uint32_t seed, fdf_model* d_models,
+                           uint8_t* d_inliers, void* d_scratch, uint64_t scratch_bytes,
+                           void* stream) {
+    RansacLayout L;
+    if (!ctx || ransac_layout(n_frames, q_cap, n_hyp, &L) != FDF_OK ||
+        t_cap > fdfk::kMatchMaxCap || !fundamental_values_ok(coords, threshold))
+        return FDF_ERR_ARG;
+    if (n_frames == 0) return FDF_OK;
+    if (!d_matches || !d_q_offsets || !d_t_offsets || !d_q_coords || !d_t_coords || !d_models ||
+        !d_scratch || scratch_bytes < L.total || ((uintptr_t)d_matches & 7u) != 0 ||
+        ((uintptr_t)d_q_coords & 7u) != 0 || ((uintptr_t)d_t_coords & 7u) != 0 ||
+        ((uintptr_t)d_models & 7u) != 0 || ((uintptr_t)d_scratch & 255u) != 0)
+        return FDF_ERR_ARG;
+    uint8_t* base = static_cast<uint8_t*>(d_scratch);
+    fdfk::RansacParams p =
+        fundamental_params(n_frames, d_matches, d_keep, q_cap, d_q_offsets, d_q_coords, d_t_coords,
+                           t_cap, d_t_offsets, coords, threshold, d_models, d_inliers);
+    p.n_hyp = n_hyp;
+    p.seed = seed;
+    p.corr = reinterpret_cast<double*>(base + L.corr);
+    p.n_corr = reinterpret_cast<uint32_t*>(base + L.n_corr);
+    p.counts = reinterpret_cast<uint32_t*>(base + L.counts);
+    DeviceGuard guard(ctx->device);
+    return status_of(fdfk::launch_fundamental(p, reinterpret_cast<hipStream_t>(stream)));
+}
+
+int fdf_fundamental_check_device(fdf_ctx* ctx, uint32_t n_frames, const fdf_match* d_matches,
+                                 const uint8_t* d_keep, uint64_t q_cap,
+                                 const uint64_t* d_q_offsets, const void* d_q_coords,
+                                 const void* d_t_coords, uint64_t t_cap,
+                                 const uint64_t* d_t_offsets, uint32_t coords,
+                                 const fdf_model* d_models_in, float threshold,
+                                 fdf_model* d_models_out, uint8_t* d_inliers, void* stream) {
+    if (!ctx || n_frames > 65535u || q_cap > fdfk::kMatchMaxCap || t_cap > fdfk::kMatchMaxCap ||
+        !fundamental_values_ok(coords, threshold))
+        return FDF_ERR_ARG;
+    if (n_frames == 0) return FDF_OK;
+    if (!d_matches || !d_q_offsets || !d_t_offsets || !d_q_coords || !d_t_coords || !d_models_in ||
+        !d_models_out || ((uintptr_t)d_matches & 7u) != 0 || ((uintptr_t)d_q_coords & 7u) != 0 ||
+        ((uintptr_t)d_t_coords & 7u) != 0 || ((uintptr_t)d_models_in & 7u) != 0 ||
+        ((uintptr_t)d_models_out & 7u) != 0)
+        return FDF_ERR_ARG;
+    fdfk::FundamentalCheckParams p{};
+    p.r = fundamental_params(n_frames, d_matches, d_keep, q_cap, d_q_offsets, d_q_coords,
+                             d_t_coords, t_cap, d_t_offsets, coords, threshold, d_models_out,
+                             d_inliers);
+    p.models_in = reinterpret_cast<const double*>(d_models_in);
+    DeviceGuard guard(ctx->device);
+    return status_of(fdfk::launch_fundamental_check(p, reinterpret_cast<hipStream_t>(stream)));
+}
+
+int fdf_fundamental_points(fdf_ctx* ctx, const void* q_coords, const void* t_coords, size_t n_q,
+                           size_t n_t, const fdf_match* matches, const uint8_t* keep,
+                           uint32_t coords, uint32_t n_hyp, float threshold, uint32_t seed,
+                           fdf_model* model_out, uint8_t* inliers_out) {
+    RansacLayout L;
+    if (!ctx || !model_out || ransac_layout(1, n_q, n_hyp, &L) != FDF_OK ||
+        n_t > fdfk::kMatchMaxCap || !fundamental_values_ok(coords, threshold))
+        return FDF_ERR_ARG;
+    if (n_q && (!q_coords || !matches)) return FDF_ERR_ARG;
+    if (n_t && !t_coords) return FDF_ERR_ARG;
+    const uint64_t t_offs[2] = {0, n_t};                  // an asynchronous copy's source
+    Arena a(ctx);
+    const auto d_q = a.part<fdf_point>(n_q);
+    const auto d_t = a.part<fdf_point>(n_t);
+    const auto d_m = a.part<fdf_match>(n_q);
+    const auto d_keep = a.part<uint8_t>(keep ? n_q : 0);
+    const auto d_qo = a.part<uint64_t>(2);
+    const auto d_to = a.part<uint64_t>(2);
+    const auto d_model = a.part<fdf_model>(1);
+    const auto d_in = a.part<uint8_t>(inliers_out ? n_q : 0);
+    const auto d_scratch = a.part<uint8_t>(L.total);
+    if (a.open() != FDF_OK) return FDF_ERR_ALLOC;
+    if (n_q) a.upload(d_q, static_cast<const fdf_point*>(q_coords));
+    if (n_t) a.upload(d_t, static_cast<const fdf_point*>(t_coords));
+    if (n_q) a.upload(d_m, matches);
+    if (keep && n_q) a.upload(d_keep, keep);
+    a.upload_one_frame(d_qo, n_q);
+    a.upload(d_to, t_offs);
+    if (a.ok()) {
+        const int status = fdf_fundamental_device(
+            ctx, 1, a.at(d_m), keep ? a.at(d_keep) : nullptr, n_q, a.at(d_qo), a.at(d_q),
+            a.at(d_t), n_t, a.at(d_to), coords, n_hyp, threshold, seed, a.at(d_model),
+            inliers_out ? a.at(d_in) : nullptr, a.at(d_scratch), L.total, ctx->stream);
+        if (status != FDF_OK) return status;
+    }
+    a.download(model_out, d_model, 1);
+    if (inliers_out && n_q) a.download(inliers_out, d_in, n_q);
+    return a.close();
+}
+
 }  // extern "C"

@@ -1999,6 +1999,142 @@ def refine_model(q_points, t_points, matches, estimate, keep=None, model="homogr
     return (out["h"][0].reshape(3, 3).copy() if found else None), mask.astype(bool), out[0], rounds
 
 
+# RANSAC fundamental-matrix estimation (fdf_fundamental.hip; include/fdf.h has the rule).
+
+def fundamental_sample(seed, frame, hypothesis, m):
+    """The sample of one fundamental-matrix hypothesis (fdf_fundamental_sample): (the 8
+    correspondence numbers below ``m`` or None when 32 draws do not give 8 distinct ones, the
+    draws made)."""
+    idx = (ctypes.c_uint32 * 8)()
+    draws = ctypes.c_uint32()
+    for name, v in (("seed", seed), ("frame", frame), ("hypothesis", hypothesis), ("m", m)):
+        if not 0 <= int(v) <= 0xffffffff:
+            raise ValueError(f"{name} must fit u32")
+    check(_native.load().fdf_fundamental_sample(int(seed), int(frame), int(hypothesis), int(m),
+                                                idx, ctypes.byref(draws)),
+          "fdf_fundamental_sample")
+    got = list(idx)
+    return (None if got[0] == RANSAC_NONE else got), draws.value
+
+
+def fundamental_scratch_bytes(n_frames, q_cap, n_hyp):
+    """Bytes of fundamental_device's scratch tensor (fdf_fundamental_scratch_bytes)."""
+    n_frames, q_cap, n_hyp = int(n_frames), int(q_cap), int(n_hyp)
+    if not (0 <= n_frames <= 65535 and 0 <= q_cap <= _MATCH_MAX_CAP):
+        raise ValueError("at most 65535 frames and fewer than 2^32 - 1 queries")
+    if not 1 <= n_hyp <= _RANSAC_MAX_HYP:
+        raise ValueError("n_hyp must be in 1..65536")
+    v = ctypes.c_uint64()
+    check(_native.load().fdf_fundamental_scratch_bytes(n_frames, q_cap, n_hyp, ctypes.byref(v)),
+          "fdf_fundamental_scratch_bytes")
+    return v.value
+
+
+def _fundamental_sets(torch, matches, q_offsets, q_coords, t_coords, t_offsets, models,
+                      keep, inliers):
+    """The checks that fundamental_device and fundamental_check_device share: (F, q_cap, t_cap,
+    FDF_COORDS_*).  ``models``: (name, tensor) pairs."""
+    _check_matches(matches, "matches", "q_cap")
+    q_cap = matches.shape[0]
+    n = _match_frames(torch, q_offsets, t_offsets)
+    kind = _check_coords(torch, q_coords, "q_coords", "q_cap", q_cap)
+    if _check_coords(torch, t_coords, "t_coords", "t_cap") != kind:
+        raise ValueError("q_coords and t_coords must have the same type")
+    for name, t in models:
+        if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != 11 or t.shape[0] < n or \
+                not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous (F, 11) float64 tensor")
+    for t, name in ((keep, "keep"), (inliers, "inliers")):
+        if t is not None and (t.dtype != torch.uint8 or t.dim() != 1 or t.numel() < q_cap or
+                              not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous uint8 tensor with q_cap entries")
+    return n, q_cap, t_coords.shape[0], kind
+
+
+def fundamental_device(matches, q_offsets, q_coords, t_coords, t_offsets, models, scratch,
+                       keep=None, inliers=None, n_hyp=256, threshold=1.0, seed=0, stream=None,
+                       device=None):
+    """RANSAC estimation of one fundamental matrix per frame on the device
+    (fdf_fundamental_device): the epipolar outlier test of a moving camera or a stereo pair.  The
+    arguments are ransac_device's without ``model`` (track_device's ``matches``, ``status`` as
+    ``keep`` and float positions go in as they are); ``threshold`` is a Sampson distance in
+    pixels.  ``models`` (F, 11) float64 gets one fdf_model per frame (unpack_models) whose h is
+    F with [u v 1] F [x y 1]^T = 0, ``inliers`` (optional, (q_cap,) uint8) 1 for the inliers of
+    each frame's best F.  ``scratch``: a uint8 tensor of fundamental_scratch_bytes(F, q_cap,
+    n_hyp), 256-byte aligned.  The result is a pure function of the inputs and ``seed``.
+    Asynchronous on ``stream`` (default: torch's current stream)."""
+    import torch
+
+    n, q_cap, t_cap, kind = _fundamental_sets(torch, matches, q_offsets, q_coords, t_coords,
+                                              t_offsets, (("models", models),), keep, inliers)
+    n_hyp, threshold, seed = _ransac_values(n_hyp, threshold, seed)
+    if scratch.dtype != torch.uint8 or scratch.dim() != 1 or not scratch.is_contiguous() or \
+            scratch.numel() < fundamental_scratch_bytes(n, q_cap, n_hyp):
+        raise ValueError("scratch must be a uint8 tensor of fundamental_scratch_bytes(F, q_cap, "
+                         "n_hyp)")
+    if scratch.data_ptr() % 256:
+        raise ValueError("scratch must be 256-byte aligned")
+    _check_one_device("fundamental_device",
+                      [matches, q_offsets, q_coords, t_coords, t_offsets, models, scratch] +
+                      [t for t in (keep, inliers) if t is not None])
+    dev, stream = _device_stream(torch, matches, device, stream)
+    rc = _native.load().fdf_fundamental_device(
+        context(dev).handle, n, matches.data_ptr(), keep.data_ptr() if keep is not None else None,
+        q_cap, q_offsets.data_ptr(), q_coords.data_ptr(), t_coords.data_ptr(), t_cap,
+        t_offsets.data_ptr(), kind, n_hyp, threshold, seed, models.data_ptr(),
+        inliers.data_ptr() if inliers is not None else None, scratch.data_ptr(),
+        scratch.numel(), ctypes.c_void_p(stream.cuda_stream))
+    check(rc, "fdf_fundamental_device")
+
+
+def fundamental_check_device(matches, q_offsets, q_coords, t_coords, t_offsets, models_in,
+                             models_out, keep=None, inliers=None, threshold=1.0, stream=None,
+                             device=None):
+    """The caller's fundamental matrices recounted on the device (fdf_fundamental_check_device):
+    no sampling.  ``models_in`` (F, 11) float64 holds one fdf_model per frame (a stereo rig's F,
+    or fundamental_device's result to recount under another ``threshold``); ``models_out`` (may
+    be ``models_in``) gets them with n_corr and n_inliers recounted, ``inliers`` (optional) the
+    inlier bytes.  A record whose hypothesis is RANSAC_NONE holds no model and is copied.
+    Asynchronous on ``stream`` (default: torch's current stream)."""
+    import torch
+
+    n, q_cap, t_cap, kind = _fundamental_sets(torch, matches, q_offsets, q_coords, t_coords,
+                                              t_offsets, (("models_in", models_in),
+                                                          ("models_out", models_out)), keep,
+                                              inliers)
+    _, threshold, _ = _ransac_values(1, threshold, 0)
+    _check_one_device("fundamental_check_device",
+                      [matches, q_offsets, q_coords, t_coords, t_offsets, models_in, models_out] +
+                      [t for t in (keep, inliers) if t is not None])
+    dev, stream = _device_stream(torch, matches, device, stream)
+    rc = _native.load().fdf_fundamental_check_device(
+        context(dev).handle, n, matches.data_ptr(), keep.data_ptr() if keep is not None else None,
+        q_cap, q_offsets.data_ptr(), q_coords.data_ptr(), t_coords.data_ptr(), t_cap,
+        t_offsets.data_ptr(), kind, models_in.data_ptr(), threshold, models_out.data_ptr(),
+        inliers.data_ptr() if inliers is not None else None, ctypes.c_void_p(stream.cuda_stream))
+    check(rc, "fdf_fundamental_check_device")
+
+
+def estimate_fundamental(q_points, t_points, matches, keep=None, n_hyp=256, threshold=1.0, seed=0,
+                         device=0):
+    """RANSAC estimation of the fundamental matrix of the matches (fdf_fundamental_points): (F
+    as a (3, 3) float64 array with [u v 1] F [x y 1]^T = 0, or None when there is no model, the
+    (n_q,) bool inlier mask, the MODEL_DTYPE record).  The point sets, ``matches`` and ``keep``
+    are estimate_model's; ``threshold`` is a Sampson distance in pixels."""
+    q, t, kind, rec, keep = _host_pair(q_points, t_points, matches, keep)
+    n_hyp, threshold, seed = _ransac_values(n_hyp, threshold, seed)
+    out = np.zeros(1, dtype=MODEL_DTYPE)
+    mask = np.zeros(len(q), dtype=np.uint8)
+    rc = _native.load().fdf_fundamental_points(
+        context(device).handle, q.ctypes.data if len(q) else None,
+        t.ctypes.data if len(t) else None, len(q), len(t), rec.ctypes.data if len(q) else None,
+        keep.ctypes.data if keep is not None and len(q) else None, kind, n_hyp, threshold, seed,
+        out.ctypes.data, mask.ctypes.data if len(q) else None)
+    check(rc, "fdf_fundamental_points")
+    found = out["hypothesis"][0] != RANSAC_NONE
+    return (out["h"][0].reshape(3, 3).copy() if found else None), mask.astype(bool), out[0]
+
+
 # Pyramidal Lucas-Kanade tracking (fdf_track.hip; include/fdf.h has the rule).
 
 TRACK_REASONS = ("skipped", "tracked", "eigenvalue", "left the frame", "step too large")
@@ -2432,6 +2568,8 @@ __all__ = ["NORTH", "EAST", "SOUTH", "WEST", "circle", "calculate_offsets", "con
            "MODEL_DTYPE", "RANSAC_NONE", "ransac_sample", "ransac_scratch_bytes", "ransac_device",
            "unpack_models", "estimate_model",
            "refine_scratch_bytes", "refine_device", "refine_model",
+           "fundamental_sample", "fundamental_scratch_bytes", "fundamental_device",
+           "fundamental_check_device", "estimate_fundamental",
            "warp_device", "warp_array", "model_invert",
            "TRACK_REASONS", "TrackResult", "track_device", "track_array", "track_map_position",
            "track_map_displacement",

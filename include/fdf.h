@@ -42,7 +42,8 @@ extern "C" {
  * fdf_refine_scratch_bytes, fdf_refine_device and fdf_refine_points, and fdf_warp_device,
  * fdf_warp_frame and fdf_model_invert, and fdf_track_device, fdf_track_frames,
  * fdf_track_map_position and fdf_track_map_displacement (with FDF_COORDS_Q11, which only the
- * tracker accepts). */
+ * tracker accepts), and fdf_fundamental_sample, fdf_fundamental_scratch_bytes,
+ * fdf_fundamental_device, fdf_fundamental_check_device and fdf_fundamental_points. */
 #define FDF_ABI_VERSION 6
 
 /* Status codes.  Shapes the reference maps to an empty Vec return FDF_OK with 0 points. */
@@ -879,6 +880,132 @@ int fdf_refine_points(fdf_ctx* ctx, const void* q_coords, const void* t_coords, 
                       uint32_t model, const fdf_model* model_in, float threshold,
                       uint32_t n_rounds, fdf_model* model_out, uint8_t* inliers_out,
                       uint32_t* rounds_out);
+
+/*
+ * RANSAC estimation of a fundamental matrix from the matches or tracks (extension: the epipolar
+ * outlier test of a camera that moves through a 3-D scene, or of a stereo pair, where no single
+ * homography fits; OpenCV's findFundamentalMat with FM_RANSAC, the rejectWithF step of visual-
+ * inertial front ends).  The result is F with [u v 1] F [x y 1]^T = 0 for a query (x, y) and its
+ * train point (u, v).  Like the block above it is a pure function of its inputs: integer
+ * sampling, every floating-point step one IEEE binary64 operation rounded once out of + - * / and
+ * the absolute value (never fused), ties by index.
+ *
+ * Correspondences.  Exactly the RANSAC block's rule on the same arrays (matches, keep,
+ * capacities, offsets, coordinates, `coords`), numbered j = 0..M-1; fdf_track_device's d_matches
+ * and d_status (as keep) with its float positions go in as they are.
+ *
+ * Sampling.  The RANSAC block's start state and next(), sample size s = 8, up to 32 draws (16
+ * leave most hypotheses of M = 8 or 9 without eight distinct values).  M < 8: no model.
+ * (seed 1, f 0, h 0, M 100) gives 54, 11, 77, 18, 0, 8, 14, 35 after 8 draws, (1, 2, 7, 9) gives
+ * 1, 0, 8, 4, 2, 7, 6, 3 after 16, (0, 0, 0, 8) gives 5, 2, 4, 6, 7, 1, 0, 3 after 18 and
+ * (0, 0, 0, 7) nothing after 32.
+ *
+ * Fit of a sample, points k = 0..7 in sample order.
+ *  1. Normalise.  Sx = the sum of x, from +0.0 in sample order (Sx = Sx + x), Sy likewise;
+ *     cx = Sx / 8, cy = Sy / 8; d = the sum, in the same way, of (|x - cx| + |y - cy|);
+ *     s = 16 / d.  The same over (u, v) gives cu, cv, e and t = 16 / e.  The hypothesis is
+ *     invalid unless 0 < d < infinity and 0 < e < infinity.  X = (x - cx) * s, Y = (y - cy) * s,
+ *     U = (u - cu) * t, V = (v - cv) * t.
+ *  2. Rows of the 8 x 9 system A fn = 0 for Fn row-major as fn0..fn8:
+ *       A[k] = [U X, U Y, U, V X, V Y, V, X, Y, 1]   (each product U * X etc. one operation).
+ *  3. Null vector by Gauss-Jordan elimination with full pivoting (no entry is fixed at 1 in
+ *     advance: a sideways-moving camera or a rectified pair has f8 = 0 exactly).  8 steps.  A
+ *     step's pivot (r, c) is the largest |A[r][c]| over the rows and columns no earlier step
+ *     used; ties go to the lowest r, then the lowest c; a NaN magnitude never wins.  The
+ *     hypothesis is invalid if that magnitude is below 2^-20 (or none is a number).  Row r and
+ *     column c are now used.  For every other row q (the used ones too): m = A[q][c] / A[r][c]
+ *     and A[q][j] = A[q][j] - m * A[r][j] for every column j still unused.  After the 8 steps,
+ *     with c* the column left unused: fn[c*] = 1, and for each row r with its pivot column c,
+ *     fn[c] = -(A[r][c*] / A[r][c]).
+ *  4. Denormalise, F = T2^T Fn T1 with T1 = [s 0 -s cx; 0 s -s cy; 0 0 1] and T2 the same of
+ *     t, cu, cv, as this sequence.  For each row r = 0, 1, 2 of Fn
+ *       a0 = fn[3r] * s,  a1 = fn[3r+1] * s,  a2 = (fn[3r+2] - a0 * cx) - a1 * cy;
+ *     with B the three rows (a0, a1, a2), for each column c = 0, 1, 2
+ *       g0 = t * B[0][c],  g1 = t * B[1][c],  G[c] = g0,  G[3+c] = g1,
+ *       G[6+c] = (B[2][c] - g0 * cu) - g1 * cv.
+ *  5. Scale.  With k* the lowest k of the largest |G[k]| (a NaN never wins), f_k = G[k] / G[k*]
+ *     for all nine k: the division is by the signed value, so f_k* is exactly +1 and the sign of
+ *     F is canonical.  The hypothesis is invalid unless 0 < |G[k*]| < infinity and every f_k is
+ *     finite.
+ * No rank-2 projection is applied: F is the exact solution of its eight equations, the score
+ * below does not need a singular F, and callers that reject outliers do not rely on one.
+ *
+ * Score.  The Sampson distance without a division, with T = (double)threshold in pixels:
+ *   l0 = (f0 x + f1 y) + f2,  l1 = (f3 x + f4 y) + f5,  l2 = (f6 x + f7 y) + f8,
+ *   m0 = (f0 u + f3 v) + f6,  m1 = (f1 u + f4 v) + f7,
+ *   r = (u l0 + v l1) + l2,  g = ((l0 l0 + l1 l1) + m0 m0) + m1 m1;
+ * an inlier iff g > 0 and r r <= (T T) g (both false for a NaN; an infinite coordinate can make
+ * both sides infinite, which holds: clear the keep byte of such a point).  A valid hypothesis'
+ * count is its number of inliers; the best hypothesis has the largest count, ties go to the
+ * lowest h.
+ *
+ * Output.  As in the RANSAC block, in the same fdf_model record: h = the winner's f0..f8 bit for
+ * bit as fitted, n_corr = M, n_inliers, hypothesis, n_valid.  No valid hypothesis (or M < 8): h
+ * all zero, n_inliers 0, hypothesis 0xFFFFFFFF.  d_inliers (optional, q_cap bytes) gets, for every
+ * i in [qo[0], min(qo[n_frames], q_cap)) and for no other byte, 1 if i is a correspondence and an
+ * inlier of its frame's best model and 0 otherwise.
+ *
+ * Example.  A rectified pair with two bad matches.  Queries (0,0), (80,0), (0,80), (80,80),
+ * (40,20), (20,60), (60,40), (30,30), (50,70), (70,10), (10,50), (60,60); train = query +
+ * (10,0), (25,0), (31,0), (12,0), (23,0), (37,0), (14,0), (29,0), (3,0), (20,30), (18,0),
+ * (40,20); matches[i].index = i, seed 3, one frame, 8 hypotheses, T = 0.5.  Hypothesis 2 wins:
+ * 10 inliers, n_valid 8, inlier bytes 1 1 1 1 1 1 1 1 1 0 1 0, counts per hypothesis
+ * 8 8 10 9 8 8 8 8, and F is [0 0 0; 0 0 1; 0 -1 0] up to rounding:
+ *   f0 = 0x1.2680dad725570p-59    f1 = 0x1.4cc344e4093b5p-57   f2 = -0x1.338fe32749f1dp-52
+ *   f3 = -0x1.ff7ec58462d65p-58   f4 = -0x1.768667157b6c1p-59  f5 = 1
+ *   f6 = 0x1.2359a7b2aed39p-53    f7 = -0x1.ffffffffffffep-1   f8 = -0x1.b7ffffffffffcp-48
+ *
+ * fdf_fundamental_sample: host only, no context; the sample of one hypothesis in idx[0..8) and
+ * the draws made in *draws (may be NULL).  An invalid hypothesis (m < 8 included) fills idx with
+ * 0xFFFFFFFF after its 32 draws.  FDF_ERR_ARG: a NULL idx.  fdf_ransac_sample is unchanged.
+ *
+ * fdf_fundamental_scratch_bytes: host only; the size of fdf_fundamental_device's d_scratch, which
+ * is fdf_ransac_scratch_bytes' with the same errors.
+ *
+ * fdf_fundamental_device: fdf_ransac_device's arguments without `model`; three kernels,
+ * asynchronous on `stream` (NULL = the HIP null stream), no context lock, no context workspace,
+ * nothing allocated and nothing returned to the host.  The FDF_ERR_ARG list, the n_frames == 0
+ * behaviour and the bounds guarantee are fdf_ransac_device's (FDF_COORDS_Q11 is rejected).
+ *
+ * fdf_fundamental_check_device: no sampling; d_models_in[f] holds the caller's matrix (a
+ * calibrated stereo rig's, or an earlier result to recount under another threshold).  One
+ * kernel, no scratch.  Per frame: hypothesis == FDF_RANSAC_NONE: the record is copied unchanged
+ * and every inlier byte of the frame is 0.  Otherwise d_models_out[f] (d_models_out may be
+ * d_models_in) gets h, hypothesis and n_valid as they came, n_corr = M and n_inliers = the
+ * number of correspondences that the Score rule makes inliers of h under `threshold`, and
+ * d_inliers (optional) the bytes by the Output rule.  It is the counterpart of
+ * fdf_refine_device with n_rounds = 0.  FDF_ERR_ARG: n_frames > 65535, a cap of 2^32 - 1 or more,
+ * a coords value that is none of the two, a threshold that is negative or not finite; and,
+ * unless n_frames == 0 (FDF_OK, nothing written): a NULL required pointer (all but d_keep and
+ * d_inliers), matches, coordinates or models that are not 8-byte aligned.  Whatever the inputs
+ * hold, the models included, no access leaves the buffers.
+ *
+ * fdf_fundamental_points: one pair of host sets as fdf_ransac_points takes them, synchronous;
+ * inliers_out (n_q bytes) may be NULL.  Copies through device buffers allocated and freed by the
+ * call and runs the same kernels; the context's workspace and retained result are untouched.
+ */
+int fdf_fundamental_sample(uint32_t seed, uint32_t frame, uint32_t hypothesis, uint32_t m,
+                           uint32_t idx[8], uint32_t* draws);
+int fdf_fundamental_scratch_bytes(uint32_t n_frames, uint64_t q_cap, uint32_t n_hyp,
+                                  uint64_t* bytes);
+int fdf_fundamental_device(fdf_ctx* ctx, uint32_t n_frames, const fdf_match* d_matches,
+                           const uint8_t* d_keep, uint64_t q_cap, const uint64_t* d_q_offsets,
+                           const void* d_q_coords, const void* d_t_coords, uint64_t t_cap,
+                           const uint64_t* d_t_offsets, uint32_t coords, uint32_t n_hyp,
+                           float threshold, uint32_t seed, fdf_model* d_models,
+                           uint8_t* d_inliers, void* d_scratch, uint64_t scratch_bytes,
+                           void* stream);
+int fdf_fundamental_check_device(fdf_ctx* ctx, uint32_t n_frames, const fdf_match* d_matches,
+                                 const uint8_t* d_keep, uint64_t q_cap,
+                                 const uint64_t* d_q_offsets, const void* d_q_coords,
+                                 const void* d_t_coords, uint64_t t_cap,
+                                 const uint64_t* d_t_offsets, uint32_t coords,
+                                 const fdf_model* d_models_in, float threshold,
+                                 fdf_model* d_models_out, uint8_t* d_inliers, void* stream);
+int fdf_fundamental_points(fdf_ctx* ctx, const void* q_coords, const void* t_coords, size_t n_q,
+                           size_t n_t, const fdf_match* matches, const uint8_t* keep,
+                           uint32_t coords, uint32_t n_hyp, float threshold, uint32_t seed,
+                           fdf_model* model_out, uint8_t* inliers_out);
 
 /*
  * Exact bilinear resize and the scale pyramid (extension: the reference detects at one scale;

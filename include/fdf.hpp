@@ -21,6 +21,7 @@
 //   (none: ... and match)            --                   fdf::match_descriptors(q_desc, t_desc, ...)
 //   (none: ... and fit a model)      --                   fdf::estimate_model(q_points, t_points, matches, ...)
 //   (none: ... and refine it)        --                   fdf::refine_model(q_points, t_points, matches, estimate, ...)
+//   (none: ... and fit an F matrix)  --                   fdf::estimate_fundamental(q_points, t_points, matches, ...)
 //   (none: ... over a scale pyramid) --                   fdf::resize, fdf::pyramid_plan, fdf::build_pyramid
 //   (none: ... and warp by the model) --                  fdf::warp, fdf::model_invert
 //   (none: ... or track the points)  --                   fdf::track
@@ -408,6 +409,37 @@ inline RefinedModel refine_model(const std::vector<Point>& q_points,
                                  uint32_t n_rounds = 2) {
     return refine_model(q_points, t_points, matches, keep, model, estimate, threshold, n_rounds,
                         thread_context());
+}
+
+// RANSAC estimation of the fundamental matrix F of the matches, [u v 1] F [x y 1]^T = 0 for a
+// query (x, y) and its train point (u, v) (extension, fdf_fundamental_points; include/fdf.h has
+// the sampling, fit and score rules): the epipolar outlier test of a moving camera or a stereo
+// pair.  The arguments are estimate_model's without `model`; `threshold` is a Sampson distance in
+// pixels.  model.h holds F, scaled so that its largest entry is +1.
+inline ModelEstimate estimate_fundamental(const std::vector<Point>& q_points,
+                                          const std::vector<Point>& t_points,
+                                          const std::vector<Match>& matches,
+                                          const std::vector<uint8_t>* keep, uint32_t n_hyp,
+                                          float threshold, uint32_t seed, Context& ctx) {
+    if (matches.size() != q_points.size() || (keep && keep->size() != q_points.size()))
+        throw Error(FDF_ERR_ARG, "estimate_fundamental: one match and keep flag per query point");
+    ModelEstimate out;
+    out.inliers.resize(q_points.size());
+    check(fdf_fundamental_points(ctx.get(), q_points.data(), t_points.data(), q_points.size(),
+                                 t_points.size(), matches.data(), keep ? keep->data() : nullptr,
+                                 FDF_COORDS_U32, n_hyp, threshold, seed, &out.model,
+                                 out.inliers.data()),
+          "fdf_fundamental_points");
+    return out;
+}
+inline ModelEstimate estimate_fundamental(const std::vector<Point>& q_points,
+                                          const std::vector<Point>& t_points,
+                                          const std::vector<Match>& matches,
+                                          const std::vector<uint8_t>* keep = nullptr,
+                                          uint32_t n_hyp = 256, float threshold = 1.0f,
+                                          uint32_t seed = 0) {
+    return estimate_fundamental(q_points, t_points, matches, keep, n_hyp, threshold, seed,
+                                thread_context());
 }
 
 // Exact bilinear resize and the scale pyramid (extension, fdf_resize_frame and
