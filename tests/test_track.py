@@ -290,6 +290,83 @@ def test_subpixel_shift():
     assert worst_q <= worst_f + EPS
 
 
+# ---- inputs that take the five sums near their ceilings -------------------------------------------
+#
+# The device tests of tests/test_gpu_track_instances.py run these inputs through the kernel, whose
+# wave reduction splits an int64 partial sum into two ints and relies on |sum| < 2^44.  What is
+# asserted here are conditions on the inputs (through the restatement's trace), so that those
+# device runs keep reaching the magnitudes they are there for; they are no tolerance on anything.
+
+CEILING_RADII = (8, 13, 15)
+CEILING_VALUES = dict(max_iters=30, eps=EPS, min_eig=1.0)
+SUM_LIMIT = 1 << 44                      # the kernel's bound; analytically 961 * 130560^2 = 2^43.9
+
+
+@functools.lru_cache(maxsize=None)
+def ceiling_frames(kind):
+    """(prev, next), 64 x 80, of 2 x 2 blocks of 0 and 255: "shifted" moves the content by (1, 0),
+    "inverted" is 255 - prev."""
+    cells = np.random.default_rng(3).integers(0, 2, (60, 60)) * 255
+    big = np.repeat(np.repeat(cells, 2, 0), 2, 1)[:112, :112].astype(np.uint8)
+    prev = big[16:80, 16:96]
+    nxt = {"shifted": big[16:80, 15:95], "inverted": 255 - prev}[kind]
+    frames = np.stack([prev, nxt])
+    frames.setflags(write=False)
+    return frames
+
+
+def ceiling_points(start):
+    """The 3 x 3 grid of the 80 x 64 frame, 10 pixels inside: pixels ("pixel") or Q11 positions
+    (777, 1234) / 2048 pixel further ("q11")."""
+    pts = np.array([(x, y) for y in (10, 31, 53) for x in (10, 39, 69)], dtype=np.int64)
+    return pts if start == "pixel" else pts * 2048 + (777, 1234)
+
+
+@functools.lru_cache(maxsize=None)
+def ceiling_run(kind, start, radius):
+    """The restatement on every point: [(result, trace)] (one level, CEILING_VALUES)."""
+    prev, nxt = ceiling_frames(kind)
+    out = []
+    for x, y in ceiling_points(start) * (2048 if start == "pixel" else 1):
+        trace = []
+        res = tr.track_point([prev], [nxt], x, y, None, radius, trace=trace, **CEILING_VALUES)
+        out.append((res, trace))
+    return out
+
+
+def ceiling_sums(kind, start, radius):
+    """(every A, every b) over the points, as flat lists of Python integers."""
+    runs = ceiling_run(kind, start, radius)
+    return ([a for _, trace in runs for lv in trace for a in lv["A"]],
+            [b for _, trace in runs for lv in trace for pair in lv["b"] for b in pair])
+
+
+@pytest.mark.parametrize("radius", CEILING_RADII)
+@pytest.mark.parametrize("start", ["pixel", "q11"])
+@pytest.mark.parametrize("kind", ["shifted", "inverted"])
+def test_ceiling_inputs_stay_tracked_and_below_the_bound(kind, start, radius):
+    """Every point runs through all its iterations to TRACKED (no early loss that would cut the
+    sums short), and every sum, the residual included, is below the kernel's 2^44."""
+    runs = ceiling_run(kind, start, radius)
+    assert len(runs) == 9 and all(res[0] == tr.TRACKED for res, _ in runs)
+    A, b = ceiling_sums(kind, start, radius)
+    assert max(map(abs, A + b + [res[3] for res, _ in runs])) < SUM_LIMIT
+    if kind == "inverted":               # no fixed point: the iteration limit ends the level
+        assert max(res[4] for res, _ in runs) == 30
+
+
+def test_ceiling_inputs_reach_the_magnitudes():
+    A, _ = ceiling_sums("shifted", "pixel", 15)
+    print(f"shifted, pixel starts, r = 15: max |A| = 2^{np.log2(max(map(abs, A))):.2f}")
+    assert max(map(abs, A)) >= 1 << 42
+    _, b = ceiling_sums("shifted", "q11", 15)
+    print(f"shifted, Q11 starts, r = 15: b from -2^{np.log2(-min(b)):.2f} to 2^{np.log2(max(b)):.2f}")
+    assert min(b) <= -(1 << 34) and max(b) >= 1 << 34             # both signs through the split
+    _, b = ceiling_sums("inverted", "pixel", 15)
+    print(f"inverted, pixel starts, r = 15: max |b| = 2^{np.log2(max(map(abs, b))):.2f}")
+    assert max(map(abs, b)) >= 1 << 37
+
+
 # ---- argument checks before any device call --------------------------------------------------
 
 def test_exports_and_constants():
